@@ -1,6 +1,6 @@
 """Headline benchmark: images/sec of MNIST SimpleCNN DDP training on N MI355X GPUs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch_size 32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch_size 32] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -9,9 +9,9 @@ touches the GPU (no torch.cuda call, no native import); it starts
 ``torch.distributed.run`` with N fresh worker processes (RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_ADDR=127.0.0.1 / a free MASTER_PORT) as a child process - the
 reference's launcher derives N processes from world_size the same way
-(``/root/reference/train_ddp.py:221-224``) - and, unless ``--no_scaling_ref``, first a
-1-rank child run of the same config, so its ONE JSON line carries
-``scaling_efficiency`` = value(N) / (N * value(1)).  Workers assert
+(the reference's ``train_ddp.py:221-224``) - and, with ``--full`` (unless
+``--no_scaling_ref``), first a 1-rank child run of the same config, so its ONE JSON line
+carries ``scaling_efficiency`` = value(N) / (N * value(1)).  Workers assert
 ``dist.get_world_size() == N`` and the native RCCL communicator's nranks == N and report
 both (``ranks_seen``, ``rccl_nranks``), plus the data plane (``bucket_allreduce``) and
 each bucket's isolated all-reduce time (``bucket_allreduce_us``).
@@ -24,9 +24,17 @@ master weights / gradients / optimizer.  A timed step is the complete training
 step of the reference's loop: batch gather + forward + loss + backward + DDP
 bucket all-reduce (N>1) + SGD update - executed by the native fused engine (2 HIP
 kernels per step on one GPU; at N>1 3 kernels + one all-reduce per gradient bucket - the
-direct xGMI kernel, RCCL as the fallback - replayed from a hipGraph).  After the bf16
-headline the same process times the exact-fp32 engine (the reference's precision) the same
-way and reports it as ``config.fp32_images_per_sec`` (``--no_fp32`` skips it).
+direct xGMI kernel, RCCL as the fallback - replayed from a hipGraph).
+
+A plain run sets up, warms up, times the K steps, writes its outputs when
+``--dump-outputs DIR`` is given (``DIR/params.npy``: the fp32 parameters after the last timed
+step, ``DIR/loss_hist.npy``: the loss of every step of the epoch window; data, weights and
+batch order are seeded, so the same arguments give the same files) and prints the record.
+``--full`` adds what else the record can carry, each a run of its own after the headline: the
+exact-fp32 engine (the reference's precision) timed the same way
+(``config.fp32_images_per_sec``; ``--no_fp32`` skips it), at N > 1 / ``--force_allreduce``
+the comm-free step breakdown and each bucket's isolated all-reduce time, and the 1-rank
+scaling reference of a self-launch.
 
 W untimed warmup steps, then EXACTLY K timed steps bracketed by barrier +
 ``torch.cuda.synchronize()`` on both sides; the step time is the MAX over ranks;
@@ -73,6 +81,33 @@ def graph_chunk(k: int, cap: int = 100) -> int:
         if k % d == 0:
             return d
     return 1
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(dirpath, tensors, budget=DUMP_BUDGET_BYTES):
+    """``--dump-outputs``: write each named tensor as ``dirpath/<name>.npy`` (float64 stays
+    float64, everything else becomes float32; the shape is kept).  The files together stay within
+    ``budget`` bytes: a tensor over its equal share is cut down to a fixed 1-D sample - sorted
+    flat indices drawn with seed 0, the same for every run of the same shapes - so two builds
+    of the project write comparable files.  Returns {name: elements written}."""
+    import numpy as np
+
+    os.makedirs(dirpath, exist_ok=True)
+    share = budget // max(1, len(tensors)) - 1024  # (the .npy header counts too)
+    written = {}
+    for name, t in tensors.items():
+        t = t.detach().to("cpu")
+        t = t if t.dtype == torch.float64 else t.to(torch.float32)
+        keep = share // t.element_size()
+        if t.numel() > keep:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(0, t.numel(), (keep,), generator=g).sort().values
+            t = t.reshape(-1)[idx]
+        np.save(os.path.join(dirpath, name + ".npy"), t.contiguous().numpy())
+        written[name] = t.numel()
+    return written
 
 
 LAUNCH_ENV = ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")
@@ -191,7 +226,7 @@ def self_launch(args, argv):
         print(json.dumps(rec), flush=True)
         return
     ref = None
-    if not args.no_scaling_ref:
+    if args.full and not args.no_scaling_ref:
         ref = run(1)
     rec = run(n)
     rec.setdefault("config", {})["launcher"] = "self (torch.distributed.run child)"
@@ -322,6 +357,14 @@ def main():
     ap.add_argument("--no_scaling_ref", action="store_true",
                     help="self-launch: skip the 1-rank reference run (scaling_efficiency null)")
     ap.add_argument("--launch_timeout", type=float, default=900.0, help="self-launch: per-child seconds")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run everything else the record can carry: the exact-fp32 "
+                         "engine, at N>1 / --force_allreduce the comm-free step breakdown and each bucket's "
+                         "isolated all-reduce time, on a self-launch the 1-rank scaling reference "
+                         "(the --no_* switches still take single parts out)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps rank 0 writes what the timed path left behind as "
+                         "DIR/<name>.npy (float32): the parameters after the last step and the loss history")
     argv = sys.argv[1:]
     args = ap.parse_args(argv)
     launched = all(k in os.environ for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"))
@@ -527,13 +570,16 @@ def main():
     placement_main = dict(placement, dist_mode_run=eo.dist_mode)
     ms = dt * 1000.0 / args.steps
     img_s = ws * args.batch_size * args.steps / dt
-    bucket_us = eng.measure_bucket_allreduce() if (ws > 1 or force) else None  # after the timed region
+    if args.dump_outputs and rank == 0:  # what the timed steps left behind, before anything else runs
+        dump_outputs(args.dump_outputs, {"params": fs.params, "loss_hist": eng.t["loss_hist"]})
+    # everything below the headline is --full's: a plain run ends with the record
+    bucket_us = eng.measure_bucket_allreduce() if args.full and (ws > 1 or force) else None  # after the timed region
     # what the multi-GPU step costs over the one-GPU step.  Every rank times the
     # same config as a comm-free local engine (the ws=1 chain: 2 kernels, fc role fused) right
     # after the headline, untimed for the metric; the difference is the exposed communication
     # (+ the dist chain's extra kernels), the rest is local compute.
     breakdown = None
-    if (ws > 1 or force) and not args.no_breakdown:
+    if args.full and (ws > 1 or force) and not args.no_breakdown:
         dtl, engl, _, _, _, _ = timed_run(args.dtype, local=True)
         loc_us = dtl * 1e6 / args.steps
         step_us = dt * 1e6 / args.steps
@@ -561,7 +607,7 @@ def main():
     # the reference's own precision (fp32 nn.Conv2d / nn.Linear, /root/reference/model.py:8-16):
     # the exact-fp32 engine timed the same way, after the headline
     fp32 = None
-    if args.dtype == "bf16" and not args.no_fp32:
+    if args.full and args.dtype == "bf16" and not args.no_fp32:
         dt32, eng32, _, _, _, _ = timed_run("fp32")
         fp32 = {"images_per_sec": round(ws * args.batch_size * args.steps / dt32, 1),
                 "ms_per_step": round(dt32 * 1000.0 / args.steps, 5),
@@ -712,6 +758,10 @@ def bench_resnet(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     img_s = ws * B * args.steps / dt
+    if args.dump_outputs and rank == 0:  # the last step's loss and the parameters it left
+        dump_outputs(args.dump_outputs, {
+            "loss": loss.detach().reshape(1),
+            "params": torch.cat([p.detach().reshape(-1).float() for p in model.parameters()])})
     if rank == 0:
         print(json.dumps({
             "metric": "images/sec ResNet-18 DDP (BASELINE config 5)", "value": round(img_s, 1),

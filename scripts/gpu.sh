@@ -6,9 +6,9 @@
 # tasks (each GPU step runs under its own timeout; the first failure ends the call):
 #   tests [pytest -k expr]     pytest -m gpu (one process), log in pytest_gpu.log
 #   smoke                      __graft_entry__.smoke()
-#   bench [bench args]         driver-shaped bench (--steps 20 --warmup 5), then 1000 steps
+#   bench [bench args]         driver-shaped bench (--full --steps 20 --warmup 5), then 1000 steps
 #   trace [bench args]         rocprofv3 kernel trace of the driver-shaped run + per-step table
-#   stats [bench args]         rocprofv3 --kernel-trace --stats of a 200-step run
+#   stats [bench args]         rocprofv3 --kernel-trace --stats of a 200-step --full run
 #   ab <envA> <envB> [n] [bench args]   alternate two env settings (e.g. DDP_AMD_GRAPH_UPLOAD=0
 #                              vs DDP_AMD_GRAPH_UPLOAD=1) over n rounds of driver-shaped +
 #                              1000-step runs; "so=<path>" as an env selects another _C.so
@@ -33,9 +33,9 @@ PYT="python -u -m pytest -x -v --timeout 120 --timeout-method thread"
 run_tests() { T 1100 $PYT -m gpu tests ${1:+-k "$1"} > "$out/pytest_gpu.log" 2>&1; rc=$?; tail -3 "$out/pytest_gpu.log"; return $rc; }
 run_smoke() { T 300 python -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.log" 2>&1 && cat "$out/smoke.log"; }
 run_bench() {
-  T 300 python bench.py --steps 20 --warmup 5 "$@" > "$out/bench_driver.json" 2>> "$out/err.log" &&
+  T 300 python bench.py --full --steps 20 --warmup 5 "$@" > "$out/bench_driver.json" 2>> "$out/err.log" &&
     echo "driver-shaped: $(cat "$out/bench_driver.json")" &&
-    T 300 python bench.py "$@" > "$out/bench.json" 2>> "$out/err.log" &&
+    T 300 python bench.py --full "$@" > "$out/bench.json" 2>> "$out/err.log" &&
     echo "1000 steps: $(cat "$out/bench.json")"
 }
 run_trace() {
@@ -44,7 +44,7 @@ run_trace() {
     python scripts/step_trace.py "$out/trace" 20 > "$out/step_trace.md" && cat "$out/step_trace.md"
 }
 run_stats() {
-  T 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/prof" -- python bench.py --steps 200 \
+  T 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/prof" -- python bench.py --full --steps 200 \
       --warmup 20 "$@" > "$out/stats_bench.json" 2>> "$out/err.log" &&
     f=$(find "$out/prof" -name '*kernel_stats.csv' | head -1) && cp "$f" "$out/kernel_stats.csv" &&
     head -12 "$out/kernel_stats.csv"
@@ -85,7 +85,7 @@ run_rehearse() {
   export DDP_AMD_XGMI_GRID_CAP=${DDP_AMD_XGMI_GRID_CAP:-16} DDP_AMD_XGMI_TIMEOUT_S=${DDP_AMD_XGMI_TIMEOUT_S:-20}
   for n in ${@:-4 8}; do
     T 240 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 \
-      --master-port $((29500 + n)) bench.py --gpus $n --backend gloo --comm xgmi --steps 200 --warmup 20 \
+      --master-port $((29500 + n)) bench.py --full --gpus $n --backend gloo --comm xgmi --steps 200 --warmup 20 \
       --no_comm_calibration > "$out/bench_n$n.log" 2>&1 || { echo "n=$n failed"; return 1; }
     tail -1 "$out/bench_n$n.log"
   done

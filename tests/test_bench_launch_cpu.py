@@ -141,3 +141,28 @@ def test_kernels_per_step_record():
     # dist_mode 4: a graph of 5 steps with 4 step heads (the first step's forward stands alone)
     assert bench.kernels_per_step(eng(pair=True, steps=5, heads=4)) == 2.2
     assert bench.kernels_per_step(eng(pair=True, steps=100, heads=99)) == 2.01
+
+
+def test_dump_outputs_writes_float_npy_within_the_budget(tmp_path):
+    """``--dump-outputs``: float32 (float64 kept) ``.npy`` files in flat order; a tensor over
+    its share of the byte budget is cut to the same seeded sample on every call."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, REPO)
+    import bench
+
+    a = torch.arange(12, dtype=torch.bfloat16).reshape(3, 4)
+    b = torch.linspace(0, 1, 5, dtype=torch.float64)
+    n = bench.dump_outputs(str(tmp_path / "x"), {"a": a, "b": b})
+    assert n == {"a": 12, "b": 5}
+    ra, rb = np.load(tmp_path / "x" / "a.npy"), np.load(tmp_path / "x" / "b.npy")
+    assert ra.dtype == np.float32 and ra.shape == (3, 4) and (ra == a.float().numpy()).all()
+    assert rb.dtype == np.float64 and (rb == b.numpy()).all()
+    big = torch.arange(100000, dtype=torch.float32)
+    for d in ("y", "z"):
+        n = bench.dump_outputs(str(tmp_path / d), {"big": big, "b": b}, budget=2 * (4096 + 1024))
+        assert n == {"big": 1024, "b": 5}
+    y, z = np.load(tmp_path / "y" / "big.npy"), np.load(tmp_path / "z" / "big.npy")
+    assert y.shape == (1024,) and (y == z).all() and (np.diff(y) >= 0).all() and y.max() > 50000
+    assert sum(os.path.getsize(tmp_path / "y" / f) for f in os.listdir(tmp_path / "y")) <= 2 * (4096 + 1024)

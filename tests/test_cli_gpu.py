@@ -16,7 +16,6 @@ import torch
 pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/checkpoints/epoch_0.pt"
 
 
 def _train(cwd, *args, expect_rc=0, timeout=180):
@@ -45,15 +44,19 @@ def test_cli_train_save_resume(tmp_path):
     assert ck["epoch"] == 0 and list(ck) == ["epoch", "model", "optimizer"]
     for k, v in ck["model"].items():
         assert v.device.type == "cpu" and v.dtype == torch.float32 and torch.isfinite(v).all(), k
-    if os.path.exists(REF):  # schema identical to the reference's own checkpoint
-        ref = torch.load(REF, weights_only=True)
-        assert list(ck["model"].keys()) == list(ref["model"].keys())
-        assert ck["model"]._metadata == ref["model"]._metadata
-        for k, v in ref["model"].items():
-            assert ck["model"][k].shape == v.shape and ck["model"][k].stride() == v.stride(), k
-        assert ck["optimizer"] == {"state": {}, "param_groups": ref["optimizer"]["param_groups"]}
-        za, zb = zipfile.ZipFile(REF), zipfile.ZipFile(ck_dir / "epoch_0.pt")
-        assert [i.filename for i in za.infolist()] == [i.filename for i in zb.infolist()]
+    # schema identical to the reference's own checkpoint (rebuilt from its recorded skeleton)
+    from test_checkpoint import _reference_checkpoint
+
+    (tmp_path / "reference").mkdir()
+    ref_path = _reference_checkpoint(tmp_path / "reference", 0)
+    ref = torch.load(ref_path, weights_only=True)
+    assert list(ck["model"].keys()) == list(ref["model"].keys())
+    assert ck["model"]._metadata == ref["model"]._metadata
+    for k, v in ref["model"].items():
+        assert ck["model"][k].shape == v.shape and ck["model"][k].stride() == v.stride(), k
+    assert ck["optimizer"] == {"state": {}, "param_groups": ref["optimizer"]["param_groups"]}
+    za, zb = zipfile.ZipFile(ref_path), zipfile.ZipFile(ck_dir / "epoch_0.pt")
+    assert [i.filename for i in za.infolist()] == [i.filename for i in zb.infolist()]
     # re-run with more epochs: auto-resume at epoch 1
     out2 = _train(tmp_path, "--epochs", "2", "--batch_size", "32", "--max_steps", "30")
     assert "Rank 0: Starting epoch 1" in out2 and "Starting epoch 0" not in out2
@@ -170,10 +173,32 @@ def _bench(*args, timeout=240):
 def test_bench_fuse_level0_keeps_the_fp32_record():
     """``--fuse_level 0`` is an advertised choice; the exact-fp32 run after
     the bf16 headline has no level-0 chain and times level 1 instead of failing the bench."""
-    r = _bench("--steps", "4", "--warmup", "1", "--fuse_level", "0")
+    r = _bench("--steps", "4", "--warmup", "1", "--fuse_level", "0", "--full")
     c = r["config"]
     assert r["n_gpus"] == 1 and r["value"] > 0 and c["fuse_level"] == 0
     assert c["fp32_images_per_sec"] and c["fp32_images_per_sec"] > 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run times the headline only (no exact-fp32 run: that is ``--full``'s), reports
+    the step time of exactly ``--steps`` steps, and ``--dump-outputs`` writes the parameters
+    after the last timed step and the loss history as float32 ``.npy`` files."""
+    import numpy as np
+
+    d = tmp_path / "out"
+    r = _bench("--gpus", "1", "--steps", "6", "--warmup", "2", "--dump-outputs", str(d))
+    c = r["config"]
+    assert r["steps"] == 6 and r["ms_per_step"] > 0 and r["dtype"] == "bf16"
+    assert abs(r["value"] - 32 * 1000.0 / r["ms_per_step"]) <= 1e-3 * r["value"]
+    assert c["fp32_images_per_sec"] is None and c["step_breakdown"] is None
+    assert sorted(os.listdir(d)) == ["loss_hist.npy", "params.npy"]
+    p, h = np.load(d / "params.npy"), np.load(d / "loss_hist.npy")
+    # (the flat parameter space: 520,586 parameters plus each tensor's alignment padding)
+    assert p.dtype == np.float32 and p.ndim == 1 and 520586 <= p.size < 520586 + 6 * 64
+    assert np.isfinite(p).all() and np.abs(p).max() > 0
+    # 2 warm-up + 6 timed steps of one epoch window: 8 losses, the untouched rest is zero
+    assert h.dtype == np.float32 and np.isfinite(h).all()
+    assert (h[:8] > 0).all() and not h[8:].any()
 
 
 def test_bench_forced_dist_record():
@@ -182,7 +207,7 @@ def test_bench_forced_dist_record():
     timing chose (both buckets' all-reduces in one launch, alone or carrying the next
     forward), the per-step
     breakdown against the comm-free engine, and the plan's cost source."""
-    r = _bench("--steps", "20", "--warmup", "5", "--force_allreduce", "--no_fp32")
+    r = _bench("--steps", "20", "--warmup", "5", "--force_allreduce", "--no_fp32", "--full")
     c = r["config"]
     assert c["force_allreduce"] and c["bucket_allreduce"].startswith("xgmi")
     assert c["pair_allreduce"] and not c["inlaunch_allreduce"]
