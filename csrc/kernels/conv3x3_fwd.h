@@ -114,6 +114,7 @@ __global__ __launch_bounds__(NW * 64, OCC * NW / 4) void conv3x3_fwd_kernel(  //
     T* __restrict__ Y, int B, int H, int W, int Cin, int Cout,
     const T* __restrict__ wfc, float* __restrict__ fc_part, C1Src c1, FwdDz dzo) {
   constexpr bool MRG = false;
+  constexpr bool NOA2 = false;
   const FwdMerge mg{};
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int bx = (int)blockIdx.x, by = (int)blockIdx.y;
@@ -128,6 +129,7 @@ __device__ __forceinline__ void fwd_body(
     const int bx, const int by, const T* __restrict__ X, const T* __restrict__ Wt, const float* __restrict__ bias,
     T* __restrict__ Y, int B, int H, int W, int Cin, int Cout, const T* __restrict__ wfc,
     float* __restrict__ fc_part, const C1Src& c1, const FwdDz& dzo, const FwdMerge& mg) {
+  constexpr bool NOA2 = false;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 #include "kernels/conv3x3_fwd_body.inc.h"
 }

@@ -1,7 +1,9 @@
 // The forward conv kernel's body - NOT a self-contained header: included inside
 // conv3x3_fwd.h's conv3x3_fwd_kernel (the plain forward) and fwd_body (the step head's
 // forward, a device function), which both define X, Wt, bias, Y, B, H, W, Cin, Cout, wfc,
-// fc_part, c1, dzo, mg, bx, by, MRG and smem before including it.  One body, two codegens:
+// fc_part, c1, dzo, mg, bx, by, MRG, NOA2 and smem before including it (NOA2: the a2 store is
+// compiled out - the inference kernel, infer.hip, whose logits nobody re-reads a2 for, and
+// which publishes its partials write-through like DZ).  One body, two codegens:
 // as a device function called by a wrapper kernel the OCC 2 plain forward spilled 22 VGPRs
 // (116 -> 128 + 92 B scratch), and as the kernel itself the step head measured 3 us slower
 // (677k vs 720k img/s forced dist_mode 4, same call, profiles/r6_dist/ab_head_codegen.txt).
@@ -265,13 +267,13 @@
       float q[4] = {v0, v1, v2, v3};  // the values actually stored (what backward re-reads)
       if constexpr (F32) {
         // (DZ: stored after the partial logits are published - see the dZ2 section)
-        if constexpr (!DZ) {
+        if constexpr (!DZ && !NOA2) {
           if (valid[pt]) st_wt(reinterpret_cast<float4*>(Y + Pp[pt] * Cout + co), make_float4(v0, v1, v2, v3));
         }
         if constexpr (DZ) a2q[pt][t] = make_float4(v0, v1, v2, v3);
       } else {
         const uint2 pk = pack4(v0, v1, v2, v3);
-        if constexpr (!DZ) {
+        if constexpr (!DZ && !NOA2) {
           if (valid[pt]) st_wt(reinterpret_cast<uint2*>(Y + Pp[pt] * Cout + co), pk);  // a2: write-through
         }
         unpack4(pk, q);
@@ -340,7 +342,7 @@
         }
       }
       float* dst = fc_part + ((long)bx * 2 + slot) * NOF + o;
-      if constexpr (DZ) st_wt(dst, acc_o);  // read by the other blocks of the image in-launch
+      if constexpr (DZ || NOA2) st_wt(dst, acc_o);  // read by the other blocks of the image in-launch
       else *dst = acc_o;
     }
   }

@@ -105,6 +105,31 @@ void conv3x3_wgrad(const bf16_t* dY, const bf16_t* Yact, const bf16_t* X, float*
 void conv3x3_wgrad(const float* dY, const float* Yact, const float* X, float* slab, int B,
                    int H, int W, int Cin, int Cout, int R, hipStream_t s, const C1Src* c1 = nullptr);
 
+// ---- SimpleCNN inference (infer.hip) --------------------------------------------------
+// One launch per evaluation batch: the training forward's body without the a2 store, then a
+// wait-free tail - the block that takes an image's last ticket sums its logits (the training
+// step's fixed order), adds the fc bias and writes the prediction (lowest-index maximum),
+// whether it equals the label, the loss (xent_row_dl's arithmetic, unscaled) and, when
+// `logits` is given, the logits.  Rows come from c1.x / c1.labels through c1.bi (clamped).
+// Scratch owned by the caller: fc_part [infer_blocks(B, pxt)][2][10] floats and img_cnt
+// [B][FWD_DZ_CNT_STRIDE] ints, zero on first use (every launch leaves them zero).  Wt / wfc:
+// the conv2 weight (OHWI) and the fc weight in the FCFRAG order, bf16 or exact fp32.
+struct InferOut {
+  int* pred = nullptr;         // [B]
+  int* correct = nullptr;      // [B] 1 / 0
+  float* loss_rows = nullptr;  // [B]
+  float* logits = nullptr;     // [B][10], optional
+};
+int infer_blocks(int B, int pxt);
+void simplecnn_infer(const bf16_t* Wt, const float* bias, const bf16_t* wfc, const float* fc_bias, int B, int pxt,
+                     const C1Src& c1, float* fc_part, int* img_cnt, const InferOut& out, hipStream_t s);
+void simplecnn_infer(const float* Wt, const float* bias, const float* wfc, const float* fc_bias, int B, int pxt,
+                     const C1Src& c1, float* fc_part, int* img_cnt, const InferOut& out, hipStream_t s);
+// tot_correct[0] += sum correct[0, n); tot_loss[0] continues its fp64 running sum over
+// loss_rows[0, n) in index order (one block; the order is fixed)
+void infer_totals(const int* correct, const float* loss_rows, int n, long long* tot_correct, double* tot_loss,
+                  hipStream_t s);
+
 // ---- general NHWC implicit-GEMM convolution (conv_gemm.hip) ------------------------
 struct ConvGeom {
   int N, H, W, Cin, OH, OW, Cout, KH, KW, stride, pad;

@@ -155,6 +155,7 @@ void stamps_set_conv3x3_bwd(void*);
 void stamps_set_linear(void*);
 void stamps_set_xent(void*);
 void stamps_set_allreduce(void*);
+void stamps_set_infer(void*);
 void stamps_set(void* p) {
   stamps_set_optim(p);
   stamps_set_conv1(p);
@@ -163,6 +164,7 @@ void stamps_set(void* p) {
   stamps_set_linear(p);
   stamps_set_xent(p);
   stamps_set_allreduce(p);
+  stamps_set_infer(p);
 }
 
 }  // namespace ddp_amd

@@ -2,9 +2,10 @@
 the reference's CPU DataLoader and the HBM-resident device loader."""
 from .imagenet import DeviceImageLoader, DeviceImages, synthetic_imagenet
 from .loader import DeviceMNIST, DeviceMNISTLoader, get_dataloader
-from .mnist import MNISTDataset, load_mnist, mnist_available, read_idx, synthetic_mnist
+from .mnist import (MNISTDataset, load_mnist, mnist_available, read_idx, synthetic_mnist,
+                    synthetic_mnist_test)
 from .sampler import ShardedSampler, epoch_indices, num_samples, steps_per_epoch
 
 __all__ = ["DeviceImageLoader", "DeviceImages", "synthetic_imagenet", "DeviceMNIST", "DeviceMNISTLoader", "get_dataloader", "MNISTDataset", "load_mnist",
-           "mnist_available", "read_idx", "synthetic_mnist", "ShardedSampler", "epoch_indices",
+           "mnist_available", "read_idx", "synthetic_mnist", "synthetic_mnist_test", "ShardedSampler", "epoch_indices",
            "num_samples", "steps_per_epoch"]

@@ -414,6 +414,7 @@ class FusedSimpleCNNEngine:
         self._captured = 0
         self.steps_done = 0
         self._need_barrier = world_size > 1
+        self._evaluators = {}  # {pxt: FusedEvaluator} (the inference kernel's scratch)
 
     # ------------------------------------------------------------------ start-up chain check
     def conservative_cfg(self) -> dict | None:
@@ -731,6 +732,39 @@ class FusedSimpleCNNEngine:
             out.append(round(e0.elapsed_time(e1) * 1000.0 / iters, 2))
         self._check_xgmi("bucket timing")
         return out
+
+    # ------------------------------------------------------------------ evaluation
+    def eval_operands(self) -> dict:
+        """What the training forward reads - conv1's parameters, the conv2 OHWI weight (bf16
+        shadow / fp32 master), b2, the fc weight in the FCFRAG order and the fc bias - all kept
+        current by the fused SGD, so an evaluation needs no refresh."""
+        fs, t = self.fs, self.t
+        v = lambda n: fs.view(fs.params, n).detach().reshape(-1)  # noqa: E731
+        f32 = self.dtype == "fp32"
+        return dict(w1=v("net.0.weight"), b1=v("net.0.bias"),
+                    w2=v("net.2.weight") if f32 else t["w2_bf16"], b2=v("net.2.bias"),
+                    wfc_frag=t["wfc_frag32"] if f32 else t["wfc_frag"], bfc=v("fl.bias"))
+
+    def evaluate(self, data: DeviceMNIST, batch_size: int = 1000, indices=None, pxt: int = 2,
+                 want_logits: bool = False):
+        """Accuracy and loss of the CURRENT parameters over rows ``indices`` (default: all) of
+        ``data``: one fused inference launch per batch (ragged last batch included), eagerly on
+        the engine's stream - behind whatever training work is queued - with scratch of its
+        own.  Returns an :class:`~ddp_amd.engine.evaluation.EvalResult` (``correct``, ``count``,
+        ``loss_sum`` and the per-image ``pred`` / ``loss`` tensors).  ``pxt`` = the engine's
+        ``opts.pxt_fwd`` reproduces the training forward's summation order bit for bit."""
+        from .evaluation import FusedEvaluator
+
+        ev = self._evaluators.get(pxt)
+        if ev is None:
+            ev = self._evaluators[pxt] = FusedEvaluator(self.fs.params.device, self.dtype, pxt)
+        self.sync_from_torch()  # (the split / index tensors may have been made on torch's stream)
+        with torch.cuda.stream(self.stream):
+            res = ev.run(data, self.eval_operands(), batch_size, indices, want_logits)
+        for out in (res.pred, res.loss, res.logits, res.correct_rows):
+            if out is not None:
+                out.record_stream(torch.cuda.current_stream())
+        return res
 
     # ------------------------------------------------------------------ epoch
     def start_epoch(self, epoch: int):

@@ -74,11 +74,25 @@ class TrainOptions:
     dtype: str = "bf16"               # GPU compute precision: bf16 | fp32 (exact fp32 MFMA, reference precision)
     verify_replicas: bool = False     # after every epoch: all ranks' parameters (+ momentum) bitwise equal, or raise
     stall: tuple | None = None        # (epoch, rank, seconds): that rank sleeps before the epoch's first step
+    eval_every: int = 0               # evaluate the held-out split after every Nth epoch (0: never)
+    eval_batch_size: int = 1000       # images per evaluation launch / forward
+    eval_only: bool = False           # resume from the newest checkpoint, evaluate, exit
+
+
+def validate_options(opts: TrainOptions):
+    """Option combinations that cannot run (checked by the CLI before any process starts, and
+    by every rank)."""
+    if opts.eval_every < 0 or opts.eval_batch_size < 1:
+        raise ValueError("--eval_every must be >= 0 and --eval_batch_size >= 1")
+    if opts.model == "resnet18" and (opts.eval_every or opts.eval_only):
+        raise ValueError("--eval_every / --eval_only evaluate SimpleCNN on the MNIST test split; the synthetic "
+                         "ImageNet set of --model resnet18 has no held-out split")
 
 
 def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
               opts: TrainOptions | None = None):
     opts = opts or TrainOptions()
+    validate_options(opts)
     backend = setup(rank=rank, world_size=world_size, backend=opts.backend,
                     timeout_s=opts.pg_timeout_s, device=opts.device)
     # RCCL means the GPU; gloo means the GPU only when it was asked for explicitly (a gloo
@@ -132,6 +146,12 @@ def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
     else:
         loader, sampler = get_dataloader(batch_size, world_size, rank, root=opts.data_root,
                                          source=opts.data, num_workers=opts.num_workers)
+    edata = None
+    if opts.eval_every or opts.eval_only:
+        timgs, tlabels, tsrc = load_mnist(opts.data_root, opts.data, split="test")
+        edata = DeviceMNIST(timgs, tlabels, device, tsrc)
+        if rank == 0:
+            print(f"Rank {rank}: Eval split: {tsrc} ({len(edata)} images)", flush=True)
     print(f"Rank {rank}: Dataloader ready", flush=True)
     loss_fn = CrossEntropyLoss()
     opt = FusedSGD(model, lr=opts.lr, momentum=opts.momentum, weight_decay=opts.weight_decay)
@@ -144,6 +164,15 @@ def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
         print(f"Rank {rank}: No checkpoint found, starting from scratch.", flush=True)
     elif rank == 0:
         print(f"Rank {rank}: Resumed from {path}, starting at epoch {start_epoch}", flush=True)
+
+    if opts.eval_only:
+        if path is None:
+            raise FileNotFoundError(f"--eval_only: no checkpoint under {opts.checkpoint_dir!r}")
+        # a bare model's parameters: the fused kernel's operands are built from them
+        res = run_eval(model, None, edata, device, opts, rank, world_size, fused)
+        _log_eval(rank, start_epoch - 1, res)
+        cleanup()
+        return model
 
     engine = None
     if fused:
@@ -196,8 +225,12 @@ def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
         if on_gpu:
             torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+        ev = None
+        if opts.eval_every and (epoch + 1) % opts.eval_every == 0:
+            ev = run_eval(model, engine, edata, device, opts, rank, world_size, fused)
+            _log_eval(rank, epoch, ev)
         _record_metrics(opts, rank, world_size, epoch, nsteps, batch_size, dt,
-                        samples_processed(nsteps, batch_size, len(sampler)))
+                        samples_processed(nsteps, batch_size, len(sampler)), ev)
 
         if opts.verify_replicas and world_size > 1:
             verify_replicas(fs, opt, rank, world_size, epoch)
@@ -207,6 +240,28 @@ def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
             dist.barrier()  # B13: nobody races past a half-written checkpoint
     cleanup()
     return model
+
+
+def run_eval(model, engine, edata, device, opts, rank: int, world_size: int, fused: bool):
+    """This rank's shard of the held-out split (:func:`eval_shard`: every image on exactly one
+    rank), then the totals over all ranks.  Fused GPU path: the inference kernel (on the
+    engine's stream with the engine's operands, or built from the bare model's parameters);
+    module path and CPU: the model's forward under ``no_grad``.  Collective."""
+    from .evaluation import all_reduce_result, eval_shard, evaluate
+
+    idx = eval_shard(len(edata), world_size, rank)
+    if engine is not None:
+        res = engine.evaluate(edata, opts.eval_batch_size, idx)
+    else:
+        res = evaluate(model, edata, device, opts.dtype, opts.eval_batch_size, idx,
+                       engine="fused" if fused else "module")
+    return all_reduce_result(res)
+
+
+def _log_eval(rank: int, epoch: int, res):
+    if rank == 0:
+        print(f"Epoch {epoch} | Eval | Loss: {res.mean_loss:.4f} | Accuracy: {100.0 * res.accuracy:.2f}% "
+              f"({res.correct}/{res.count})", flush=True)
 
 
 def module_comm(comm: str) -> str:
@@ -417,8 +472,9 @@ def samples_processed(nsteps: int, batch: int, samples_per_rank: int) -> int:
     return min(nsteps * batch, samples_per_rank)
 
 
-def _record_metrics(opts, rank, ws, epoch, nsteps, batch, dt, samples):
-    """``samples``: images this rank processed in the epoch (:func:`samples_processed`)."""
+def _record_metrics(opts, rank, ws, epoch, nsteps, batch, dt, samples, ev=None):
+    """``samples``: images this rank processed in the epoch (:func:`samples_processed`);
+    ``ev``: the epoch's evaluation totals, when it ran (eval_loss / eval_accuracy keys)."""
     if not opts.metrics_json or rank != 0:
         return
     import json
@@ -426,5 +482,7 @@ def _record_metrics(opts, rank, ws, epoch, nsteps, batch, dt, samples):
     rec = {"epoch": epoch, "world_size": ws, "steps": nsteps, "batch_size": batch,
            "samples_per_rank": samples, "seconds": dt,
            "images_per_sec_aggregate": samples * ws / dt if dt > 0 else None}
+    if ev is not None:
+        rec["eval_loss"], rec["eval_accuracy"] = ev.mean_loss, ev.accuracy
     with open(opts.metrics_json, "a") as f:
         f.write(json.dumps(rec) + "\n")

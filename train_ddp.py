@@ -16,7 +16,7 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from ddp_amd.engine.trainer import TrainOptions, ddp_train  # noqa: E402
+from ddp_amd.engine.trainer import TrainOptions, ddp_train, validate_options  # noqa: E402
 from ddp_amd.parallel.launcher import launch  # noqa: E402
 
 
@@ -83,6 +83,12 @@ def parse_args(argv=None):
                         "fc branch, bucket all-reduces of the 8-rank plan on the --comm plane, chain check)")
     p.add_argument("--verify_replicas", action="store_true",
                    help="after every epoch check that all ranks' parameters and momentum are bitwise equal")
+    p.add_argument("--eval_every", type=int, default=0,
+                   help="evaluate the held-out test split (sharded over the ranks, exact counts) after every "
+                        "Nth epoch; 0 = never (simplecnn)")
+    p.add_argument("--eval_batch_size", type=int, default=1000, help="images per evaluation batch")
+    p.add_argument("--eval_only", action="store_true",
+                   help="resume from the newest checkpoint, evaluate the test split, exit")
     return p.parse_args(argv)
 
 
@@ -99,9 +105,11 @@ def main(argv=None):
                         comm=a.comm, model=a.model, image_size=a.image_size,
                         num_classes=a.num_classes, dataset_size=a.dataset_size,
                         graph_module=a.graph_module, verify_replicas=a.verify_replicas,
-                        force_allreduce=a.force_allreduce,
+                        force_allreduce=a.force_allreduce, eval_every=a.eval_every,
+                        eval_batch_size=a.eval_batch_size, eval_only=a.eval_only,
                         stall=tuple(float(v) for v in a.stall_at.split(":")) if a.stall_at else None,
                         fault=tuple(int(v) for v in a.fault_at.split(":")) if a.fault_at else None)
+    validate_options(opts)
     launch(ddp_train, a.world_size, args=(a.epochs, a.batch_size, opts))
 
 
