@@ -38,8 +38,10 @@ def launch(fn: Callable, world_size: int | None = None, args: tuple = ()) -> Non
         fn(rank, ws, *args)
         return
     ws = world_size or default_world_size()
-    ensure_master_env()
     if ws == 1:
+        # no port is picked here: with MASTER_PORT unset, setup() joins over an in-process
+        # store, so a single process never races other processes for a free TCP port
         fn(0, 1, *args)
         return
+    ensure_master_env()
     torch.multiprocessing.spawn(fn, args=(ws, *args), nprocs=ws, join=True)

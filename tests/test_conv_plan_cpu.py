@@ -84,6 +84,89 @@ def test_plans_match_sweep_winners():
         assert got == ppc, (name, got)
 
 
+def _geo(N, H, W, Cin, Cout, K, s, p):
+    """Size-only stand-ins of any geometry (the planner reads sizes, never data)."""
+    OH, OW = (H + 2 * p - K) // s + 1, (W + 2 * p - K) // s + 1
+    one = torch.empty(1, dtype=BF)
+    return one.expand(N, H, W, Cin), one.expand(N, OH, OW, Cout), OH, OW
+
+
+def _halo_fits(bp, W):
+    R = bp // W
+    return R >= 1 and (R + 2) * (W + 2) <= 232
+
+
+@pytest.mark.parametrize("Cin,Cout", [(64, 64), (64, 128), (256, 512)])
+@pytest.mark.parametrize("K,s,p", [(3, 1, 1), (3, 2, 1), (1, 2, 0)])
+def test_plan_invariants_any_geometry(K, s, p, Cin, Cout):
+    """Every H, W in 1..64 (H != W included), N in {1, 3}: the invariants the launchers rely
+    on.  `train_ddp.py --image_size` reaches all of these, not only ResNet-18/224's."""
+    C = native.require()
+    s1 = K == 3 and s == 1
+    for N in (1, 3):
+        for H in range(1, 65):
+            for W in range(1, 65):
+                x, y, OH, OW = _geo(N, H, W, Cin, Cout, K, s, p)
+                P, ctx = N * OH * OW, (N, H, W)
+                for dgrad in (False, True):
+                    rows_c, k_c = (Cin, Cout) if dgrad else (Cout, Cin)
+                    for force in (-1, 1):  # auto, halo tile requested
+                        bp, bc, splits, rows, par, halo = C.conv_gemm_plan(x, y, K, K, s, p, dgrad, 0, 0, 0, -1, force)
+                        assert bp in (64, 128) and bc in (64, 128) and rows_c % bc == 0, ctx
+                        # parity classes exactly for stride-2 data gradients
+                        assert par == (1 if (dgrad and s == 2) else 0), ctx
+                        if halo:
+                            # only where the (R + 2) x (W + 2) halo of R = bp // W rows fits the LDS tile
+                            assert s1 and _halo_fits(bp, W), ctx
+                            R = bp // W
+                            nk = k_c // 32                      # K chunks of the halo kernels
+                            assert dgrad or splits > 1 or rows == N * -(-H // R), ctx
+                        else:
+                            assert force != 1 or not s1 or not (_halo_fits(128, W) or _halo_fits(64, W)), ctx
+                            taps = ((K + 1) // 2) ** 2 if par else K * K
+                            nk = taps * k_c // 32               # K-steps (of the largest parity class)
+                            Pg = P if not dgrad else N * H * W
+                            assert dgrad or splits > 1 or rows == -(-Pg // bp), ctx
+                        assert 1 <= splits <= nk, ctx
+                        assert (splits - 1) * -(-nk // splits) < nk, ctx  # no empty split
+                        if not dgrad and splits > 1:  # splitk_reduce's rows: at least 1 pixel each
+                            assert 1 <= rows <= min(512, P), ctx
+                # weight gradient chunking
+                ppc = C.conv_gemm_wgrad_ppc(x, y, K, K, s, p)
+                uses = C.conv_gemm_wgrad_uses_halo(x, y, K, K, s, p, ppc)
+                assert ppc > 0 and (ppc % 32 == 0 or uses), ctx    # the binding's own check
+                chunks = C.conv_gemm_wgrad_chunks(x, y, K, K, s, p, ppc)
+                assert chunks * ppc >= P > (chunks - 1) * ppc, ctx
+                if uses:
+                    Wp = (W + 7) & ~7
+                    assert s1 and Wp in (8, 16, 32, 56), ctx       # the launcher throws otherwise
+                    R = 224 // Wp
+                    quantum = H if H < R else 1                    # stacked groups hold whole images
+                    assert ppc % (W * quantum) == 0, ctx
+                    Hs = min(H, R)
+                    assert (R // Hs) * (Hs + 2) * (Wp + 2) <= 360, ctx  # the halo(s) fit the LDS tile
+                else:
+                    assert ppc % 32 == 0, ctx
+                # any whole-image chunk is eligible exactly when the planner's own is
+                assert C.conv_gemm_wgrad_uses_halo(x, y, K, K, s, p, N * H * W) == (uses and s1), ctx
+
+
+def test_halo_wgrad_gate_pinned():
+    """Geometries the tap-fused halo weight gradient must refuse (the per-tap GEMM runs
+    instead): widths whose 8-rounded value does not divide its 224 K slots, and small images
+    whose stacked halos exceed its 360-position LDS tile."""
+    C = native.require()
+
+    def uses(N, H, W):
+        x, y, _, _ = _geo(N, H, W, 64, 64, 3, 1, 1)
+        return C.conv_gemm_wgrad_uses_halo(x, y, 3, 3, 1, 1, C.conv_gemm_wgrad_ppc(x, y, 3, 3, 1, 1))
+
+    for H, W in ((18, 18), (10, 20), (36, 36), (3, 3), (4, 4), (3, 4), (2, 56), (1, 7), (60, 60)):
+        assert not uses(2, H, W), (H, W)
+    for H, W in ((13, 13), (5, 5), (20, 10), (25, 25), (9, 50), (6, 3), (9, 9), (7, 7), (3, 56), (50, 50)):
+        assert uses(2, H, W), (H, W)
+
+
 def test_explicit_plan_overrides_and_bad_tiles():
     C = native.require()
     x, y, _ = _shapes(2, 14, 128, 256, 3, 1, 1)

@@ -21,6 +21,41 @@ def test_bucket_plan_reproduces_reference_rebuilt_buckets():
     assert r[0][0] == 0 and r[0][0] + r[0][1] == r[1][0] and r[1][0] + r[1][1] == fs.numel
 
 
+def test_single_process_launch_needs_no_tcp_port(monkeypatch):
+    """`train_ddp.py --world_size 1`: the launcher picks no port, so setup() joins over an
+    in-process store - a port picked ahead of the rendezvous could be taken by another
+    process before TCPStore bound it (EADDRINUSE between back-to-back CLI runs on a shared
+    host).  A launcher-given MASTER_PORT is still honoured (ws > 1 defaults it)."""
+    from ddp_amd.parallel import cleanup, launch, setup
+
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        monkeypatch.delenv(k, raising=False)
+    seen = {}
+
+    def fn(rank, ws):
+        seen["port_before_setup"] = "MASTER_PORT" in os.environ
+        setup(rank, ws, backend="gloo", verbose=False, device="cpu")
+        try:
+            seen["store"] = dist.distributed_c10d._get_default_store()
+            t = torch.ones(3)
+            dist.all_reduce(t)
+            seen["sum"] = t.tolist()
+        finally:
+            cleanup(verbose=False)
+
+    try:
+        launch(fn, 1)
+    finally:  # (setup() defaults both for later readers in its process)
+        os.environ.pop("MASTER_PORT", None)
+        os.environ.pop("MASTER_ADDR", None)
+    assert seen["port_before_setup"] is False
+    store = seen["store"]
+    while hasattr(store, "underlying_store"):  # PrefixStore wrappers
+        store = store.underlying_store
+    assert isinstance(store, dist.HashStore), store
+    assert seen["sum"] == [1.0, 1.0, 1.0]
+
+
 def _worker_ddp_equivalence(rank, ws, port, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=ws)

@@ -447,8 +447,12 @@ def test_pools_and_head(C):
     assert relerr(o, a @ w.t() + b) < 1e-5
 
 
-def test_resnet18_hip_vs_cpu_fp32():
-    """Whole-network gradients of the HIP ResNet-18 vs an fp32 CPU oracle.
+@pytest.mark.parametrize("side", [64, 72])
+def test_resnet18_hip_vs_cpu_fp32(side):
+    """Whole-network gradients of the HIP ResNet-18 vs an fp32 CPU oracle, at 64 x 64 images
+    (layers 16, 8, 4, 2 wide) and 72 x 72 (18, 9, 5, 3: generic-width halo kernels, the halo
+    weight gradient on two layers and its per-tap fallback on the other two, the parity-class
+    data gradient from odd inputs, the max-pool from 36).
 
     A random-init ResNet-18 amplifies rounding through 20 BatchNorm backwards, so a
     fixed tolerance is meaningless: the bar is the precision floor, i.e. the error
@@ -464,7 +468,7 @@ def test_resnet18_hip_vs_cpu_fp32():
     cpu16.load_state_dict(cpu.state_dict())
     gpu = resnet18(num_classes=10).to(dev)
     gpu.load_state_dict(cpu.state_dict())
-    x = torch.randn(4, 3, 64, 64)
+    x = torch.randn(4, 3, side, side)
     y = torch.randint(0, 10, (4,))
     lc = F.cross_entropy(cpu(x), y)
     lc.backward()
