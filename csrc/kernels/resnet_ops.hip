@@ -587,7 +587,9 @@ __global__ __launch_bounds__(256) void xent_wave_rows_kernel(const float* __rest
       const int c = lane + 64 * m;
       if (c < C) dlogits[(long)b * C + c] = (x[m] * inv - (c == label ? 1.f : 0.f)) * gscale;
     }
-    if (lane == 0) st_wt(ws + b, mx + __logf(se) - xl);
+    // log(se) - (xl - mx), not (mx + log(se)) - xl: the latter rounds at the logits' own
+    // magnitude (an offset of 1e4 costs 5e-4 of the row's loss), xl - mx is (nearly) exact
+    if (lane == 0) st_wt(ws + b, __logf(se) - (xl - mx));
   }
   if (!last_arrival(ticket, gridDim.x, &s_last)) return;
   if (threadIdx.x == 0) {

@@ -2,6 +2,7 @@
 kernels' native layouts (NHWC activations, OHWI conv weights, [out][HW][C] fc
 weight).  Used (a) as the numerics oracle of the GPU tests and (b) by nothing
 on the GPU path - the HIP kernels are mandatory there (see ``ddp_amd.native``).
+The float64 references of the non-convolution ResNet kernels are at the end.
 """
 from __future__ import annotations
 
@@ -136,3 +137,121 @@ def simple_cnn_step_exact(params: dict, x: torch.Tensor, labels: torch.Tensor, w
     s = 1.0 / ws
     return loss, {"w1": dw1 * s, "b1": db1 * s, "w2": dw2 * s, "b2": db2 * s,
                   "wfc": dwfc * s, "bfc": dl.sum(0) * s}
+
+
+# ---------------------------------------------------------------------------------------
+# float64 CPU references of the non-convolution ResNet kernels (csrc/kernels/resnet_ops.hip,
+# xent.hip).  NHWC tensors, the kernels' own inputs (BatchNorm takes mean / invstd / gamma /
+# beta as given - nothing is recomputed); every result is unrounded float64.
+# tests/test_resnet_ops_reference_cpu.py holds them against torch's own double-precision
+# operators, tests/test_resnet_ops_elementwise_gpu.py holds the kernels against them.
+def _d(t):
+    return None if t is None else t.detach().cpu().double()
+
+
+def bn_apply64(x, mean, invstd, gamma, beta, res=None, relu=False):
+    """y = act(x * sc + (beta - mean * sc) [+ res]) with sc = invstd * gamma; x NHWC."""
+    x, mean, invstd, gamma, beta, res = map(_d, (x, mean, invstd, gamma, beta, res))
+    sc = invstd * gamma
+    y = x * sc + (beta - mean * sc)
+    if res is not None:
+        y = y + res
+    return torch.relu(y) if relu else y
+
+
+def bn_bwd64(d, x, mean, invstd, gamma, count):
+    """BatchNorm backward from the (already masked and summed) upstream gradient ``d``.
+
+    Returns a dict: ``sum_d`` = sum d, ``sum_dxh`` = sum d * xhat per channel, their
+    absolute-value companions ``abs_d`` = sum |d| and ``abs_dxh`` = sum |d * xhat| (the
+    rounding bounds of the sums), ``xh`` and
+    ``dx`` = gamma * invstd / count * (count * d - sum_d - xhat * sum_dxh)."""
+    d, x, mean, invstd, gamma = map(_d, (d, x, mean, invstd, gamma))
+    C = x.shape[-1]
+    xh = (x - mean) * invstd
+    d2, q2 = d.reshape(-1, C), (d * xh).reshape(-1, C)
+    sd, sq = d2.sum(0), q2.sum(0)
+    dx = gamma * invstd / count * (count * d - sd - xh * sq)
+    return {"sum_d": sd, "sum_dxh": sq, "abs_d": d2.abs().sum(0), "abs_dxh": q2.abs().sum(0), "xh": xh,
+            "dx": dx}
+
+
+def _pool_taps(H, W):
+    """3x3 / s2 / p1 window taps: (k, output rows, output cols, input rows, input cols)."""
+    OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    for k in range(9):
+        kh, kw = divmod(k, 3)
+        oh = [o for o in range(OH) if 0 <= 2 * o - 1 + kh < H]
+        ow = [o for o in range(OW) if 0 <= 2 * o - 1 + kw < W]
+        if oh and ow:
+            yield (k, torch.tensor(oh), torch.tensor(ow), torch.tensor([2 * o - 1 + kh for o in oh]),
+                   torch.tensor([2 * o - 1 + kw for o in ow]))
+
+
+def maxpool64(x):
+    """3x3 / stride 2 / pad 1 max pool of an NHWC tensor.
+
+    Returns ``(y, idx, bwd)``: the float64 maxima, the window index 0..8 (kh * 3 + kw) of
+    the FIRST maximum in row-major window order (torch's tie rule) as int64, and
+    ``bwd(d, dtype=torch.float64)`` which routes an upstream gradient [N,OH,OW,C] to the
+    input by those indices, summing an input pixel's (at most 4) matches in ascending
+    window order kh, kw in ``dtype``."""
+    x = _d(x)
+    N, H, W, C = x.shape
+    OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    win = torch.full((9, N, OH, OW, C), float("-inf"), dtype=torch.float64)
+    for k, oh, ow, ih, iw in _pool_taps(H, W):
+        win[k][:, oh[:, None], ow[None, :]] = x[:, ih[:, None], iw[None, :]]
+    y = win.max(0).values
+    idx = ((win == y).cumsum(0) == 0).sum(0)  # taps before the first maximum
+
+    def bwd(d, dtype=torch.float64):
+        d = d.detach().cpu().to(dtype)
+        dx = torch.zeros(N, H, W, C, dtype=dtype)
+        zero = torch.zeros((), dtype=dtype)
+        for k, oh, ow, ih, iw in _pool_taps(H, W):  # ascending k: kh, then kw
+            sel = torch.where(idx[:, oh[:, None], ow[None, :]] == k, d[:, oh[:, None], ow[None, :]], zero)
+            dx[:, ih[:, None], iw[None, :]] += sel
+        return dx
+
+    return y, idx, bwd
+
+
+def avgpool64(x):
+    """Global average pool [N,H,W,C] -> [N,C]."""
+    x = _d(x)
+    return x.reshape(x.shape[0], -1, x.shape[-1]).sum(1) / (x.shape[1] * x.shape[2])
+
+
+def avgpool_bwd64(dy, H, W):
+    """[N,C] -> [N,H,W,C]: every pixel receives dy / (H * W)."""
+    dy = _d(dy)
+    return (dy / (H * W))[:, None, None, :].expand(dy.shape[0], H, W, dy.shape[1]).contiguous()
+
+
+def xent_rows64(logits, labels):
+    """Per-row softmax cross-entropy: (loss [B], softmax p [B,C])."""
+    x = _d(logits)
+    lab = labels.detach().cpu().long()
+    z = x - x.max(1, keepdim=True).values
+    lse = z.exp().sum(1).log()
+    return lse - z[torch.arange(x.shape[0]), lab], (z - lse[:, None]).exp()
+
+
+def xent64(logits, labels, gscale=None):
+    """(mean loss, dlogits = (softmax - onehot) * gscale); gscale defaults to 1 / B."""
+    loss, p = xent_rows64(logits, labels)
+    B = p.shape[0]
+    d = p.clone()
+    d[torch.arange(B), labels.detach().cpu().long()] -= 1.0
+    return loss.mean(), d * (1.0 / B if gscale is None else gscale)
+
+
+def gemm64(A, B, bias=None, alpha=1.0, prior=None):
+    """alpha * A @ B [+ bias over columns] [+ prior]; A [M,K], B [K,N]."""
+    out = alpha * (_d(A) @ _d(B))
+    if bias is not None:
+        out = out + _d(bias)
+    if prior is not None:
+        out = out + _d(prior)
+    return out
