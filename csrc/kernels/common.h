@@ -386,19 +386,32 @@ constexpr int XENT_PRE_Q = 4;  // float4 per thread held from the prefetch to th
 // so every caller evaluates the same float operations in the same order (bit-identical).
 // Image b's raw logit o (before the bias): sum over the conv blocks kb0..kb1 touching it of
 // part[kb][slot][o] (slot 1 only for a first block that started in the previous image).
-template <typename Ld>
-__device__ __forceinline__ float xent_logit_acc(int b, int o, int HW, int CH, int NO, Ld ld) {
+// The index sequence of that sum: term j (0 <= j < XENT_MAX_BLK) reads part[xent_logit_idx]
+// (block index clamped to kb1; the clamped terms are added as +0.0f).
+__device__ __forceinline__ int xent_logit_idx(int b, int o, int HW, int CH, int NO, int j) {
   const int p0 = b * HW;
   const int kb0 = p0 / CH, kb1 = (p0 + HW - 1) / CH;
   const int slot0 = kb0 * CH == p0 ? 0 : 1;
-  float a = 0.f;
+  const int kb = min(kb0 + j, kb1);
+  return (kb * 2 + (j == 0 ? slot0 : 0)) * NO + o;
+}
+// Terms [J0, J1) of the sum added to a, j ascending; ld(j, i) returns term j's value part[i].
+// The whole sum is the ranges chained in order from +0.0f (the level-3 forward sums the
+// granules it swept in two halves; every other caller in one piece through xent_logit_acc).
+template <int J0, int J1, typename Ld>
+__device__ __forceinline__ float xent_logit_acc_range(float a, int b, int o, int HW, int CH, int NO, Ld ld) {
+  const int p0 = b * HW;
+  const int kb0 = p0 / CH, kb1 = (p0 + HW - 1) / CH;
 #pragma unroll
-  for (int j = 0; j < XENT_MAX_BLK; ++j) {
-    const int kb = min(kb0 + j, kb1);
-    const float v = ld((kb * 2 + (j == 0 ? slot0 : 0)) * NO + o);
+  for (int j = J0; j < J1; ++j) {
+    const float v = ld(j, xent_logit_idx(b, o, HW, CH, NO, j));
     a += (kb0 + j <= kb1) ? v : 0.f;
   }
   return a;
+}
+template <typename Ld>
+__device__ __forceinline__ float xent_logit_acc(int b, int o, int HW, int CH, int NO, Ld ld) {
+  return xent_logit_acc_range<0, XENT_MAX_BLK>(0.f, b, o, HW, CH, NO, [&](int, int i) { return ld(i); });
 }
 // dL[o] of one row x[0..NO) (softmax - onehot, times gscale); *loss (if o == 0 and loss)
 // = logsumexp - x[label].  label is clamped to [0, NO).

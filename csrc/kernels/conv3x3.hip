@@ -111,7 +111,7 @@ bool conv3x3_step_head(const BwdXar& x, int* done_fc, int* done_conv, const bf16
                        int* err, hipStream_t s, const ShadowSet* late) {
   const int nx = x.nblk0 + x.nblk1;
   const char* bad = !x.args ? "all-reduce arguments" : x.nblk0 < 0 || x.nblk1 <= 0 ? "the conv bucket's blocks"
-                   : !done_fc || !done_conv ? "bucket-done counters" : !dz.dz2 || !dz.img_cnt || !dz.fc_bias
+                   : !done_fc || !done_conv ? "bucket-done counters" : !dz.dz2 || !dz.gran || !dz.gen || !dz.fc_bias
                    ? "the level-3 forward's dZ2 outputs" : !wfc ? "the fc weight shadow" : !c1.x ? "the images" : nullptr;
   if (bad) throw std::runtime_error(std::string("conv3x3_step_head: missing ") + bad);
   if (!conv3x3_step_head_fits(nx, B)) return false;
@@ -146,7 +146,7 @@ static void fwd_launch(const T* X, const T* Wt, const float* bias, T* Y, int B, 
   const FwdDz dzo = dz ? *dz : FwdDz();
   if (dz) {
     if (!g || !fc || !a1x || !(pxt == 1 || pxt == 2) || !(sizeof(T) == 2 ? (void*)dz->dz2 : (void*)dz->dz2_f32) ||
-        !dz->img_cnt || !dz->fc_bias)
+        !dz->gran || !dz->gen || !dz->fc_bias)
       throw std::runtime_error("conv3x3_fwd: the level-3 dZ2 epilogue is the SimpleCNN forward with the fc "
                                "epilogue and the conv1 recompute");
     if constexpr (sizeof(T) == 2) {

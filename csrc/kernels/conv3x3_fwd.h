@@ -4,6 +4,8 @@
 // epilogue, and its MRG instantiation, the dist_mode 4 step head.
 #pragma once
 
+#include <type_traits>
+
 #include "kernels/conv3x3_body.h"
 
 namespace ddp_amd {

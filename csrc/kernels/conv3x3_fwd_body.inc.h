@@ -14,6 +14,17 @@
   constexpr int CE = P::CE;
   DDP_STAMP(STAMP_K_CONV_FWD, 0);
   DDP_GEOM_OVERRIDE();
+  // level 3: this launch's granule tag (launchers.h FwdDz), read once; never 0
+  typedef __attribute__((address_space(1))) unsigned long long gran_t;
+  // granules swept per round: all 16 terms of a logit at once, or two rounds of 8 where the 16
+  // 64-bit values would not fit (OCC 2: 128 VGPRs; exact fp32: next to its fc weight quads they
+  // would take the kernel past 256 VGPRs, one block per CU, and B = 32 off the level-3 chain)
+  constexpr int DZ_SW = (OCC == 2 || F32) ? XENT_MAX_BLK / 2 : XENT_MAX_BLK;
+  unsigned dz_epoch = 1u;
+  if constexpr (DZ) {
+    const unsigned g = *dzo.gen + 1u;
+    dz_epoch = g ? g : 1u;
+  }
   constexpr int CH = 16 * NW * PXT, NT = NW * 64;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int HW = H * W;
@@ -35,6 +46,7 @@
       if (z < c1.zero_total) c1.zero_i32[z] = 0;
     }
   Conv1Group cg;
+  int bi_base = 0;  // the step's first row (step counter x stride), read once: the level-3 labels reuse it
   if constexpr (!MRG) {
   if (A1X) cg = conv1_group_load(c1.w, c1.b, wave & 3);  // lands during the staging round
   // weights and (unless recomputed) the input rows in ONE round of loads
@@ -55,7 +67,7 @@
     // to the step's compact batch buffers, if given.
     float* sxx = reinterpret_cast<float*>(sX + XR * XS);
     const int NXX = XR + 2 * W + 2;
-    const int base = c1.bi.base();
+    const int base = bi_base = c1.bi.base();
     for (int r = threadIdx.x; r < NXX; r += NT) {
       const long Pq = Pbase - W - 1 + r;
       float v = 0.f;
@@ -341,26 +353,36 @@
           acc_o += in ? v : 0.f;
         }
       }
-      float* dst = fc_part + ((long)bx * 2 + slot) * NOF + o;
-      if constexpr (DZ || NOA2) st_wt(dst, acc_o);  // read by the other blocks of the image in-launch
-      else *dst = acc_o;
+      if constexpr (DZ) {
+        // one aligned 8-byte write-through store {tag, float bits}: the data is the flag.  Both
+        // slots always (a block inside one image publishes slot 1's +0.0f sum; nobody reads it)
+        __hip_atomic_store((gran_t*)dzo.gran + ((long)bx * 2 + slot) * NOF + o,
+                           ((unsigned long long)dz_epoch << 32) | __builtin_bit_cast(unsigned, acc_o),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      } else {
+        float* dst = fc_part + ((long)bx * 2 + slot) * NOF + o;
+        if constexpr (NOA2) st_wt(dst, acc_o);  // read by the other blocks of the image in-launch
+        else *dst = acc_o;
+      }
     }
   }
   DDP_STAMP(STAMP_K_CONV_FWD, 4);
   if constexpr (DZ) {
     // ---- level 3: dL of the block's image(s), then dZ2 of its own pixels.
-    // Hand-off (MI355X_MICROARCH.md, hand-off table row 1): the partials were stored sc1 by
-    // wave 0 (threads < 2 * NOF), which drains them and then adds 1 to each touched image's
-    // counter (one lane per counter); the same wave polls the counters with sc1 loads and
-    // reads the partials with sc1 loads; the other waves only read LDS after a barrier.
+    // Hand-off (cdna_hip_programming.md Guideline 16, recipe R2; launchers.h FwdDz): the
+    // partials were published above as tagged 8-byte granules, one aligned write-through
+    // store each - no drain, no flag.  Wave 0's lanes (slot, o) sweep the granules of every
+    // block of their image with agent-scope 8-byte loads until each carries this launch's
+    // tag; the values they then hold ARE the partials.  The other waves only read LDS after a
+    // barrier.
     const int HWi = H * W;
     const int img0 = (int)(P0 / HWi);
     const long plast = (P0 + CH < Ptot ? P0 + CH : Ptot) - 1;
     const int nimg = (int)(plast / HWi) - img0 + 1;  // 1 or 2 (CH <= HW)
     float* s_lg = s_fc + NW * PXT * 4 * NOF;          // [2][NOF] logits
     float* s_dl = s_lg + 2 * NOF;                     // [2][NOF] dL
-    // the stored a2 (write-through; the conv backward reads it): deferred out of the epilogue
-    // so that wave 0's drain before its arrival add waits for the partial logits only
+    // the stored a2 (write-through; the conv backward reads it): issued behind the granule
+    // stores (in-order stores: the epilogue's a2 stores ahead of them would delay the hand-off)
     auto store_a2 = [&]() {
 #pragma unroll
       for (int pt = 0; pt < PXT; ++pt)
@@ -373,63 +395,74 @@
         }
     };
     DDP_STAMP(STAMP_K_FWD_DZ, 0);
-    if (wave != 0) store_a2();
+    store_a2();
     if (wave == 0) {
+      const int slot = lane >= NOF ? 1 : 0, o = lane - slot * NOF;
+      const bool act = lane < 2 * NOF && slot < nimg;  // this lane owns logit o of image img0 + slot
       int label = 0;
-      if (lane < 2 * NOF) {  // the label of this thread's row, requested before the wait (its
-        // dependent-load chain overlaps the store drain below; loading it in the prologue
-        // instead measured -0.6 %: it delayed the x staging loads, profiles/r4_label)
-        const int im = img0 + (lane >= NOF ? 1 : 0);
-        if (im < B) label = c1.labels[c1.bi.row(im, c1.bi.base())];
+      float fcb = 0.f;
+      if (lane < 2 * NOF) {  // the label of this thread's row and its class's bias, requested
+        // before the sweep and first used after it (their latency overlaps it; the step counter
+        // behind the row index is the prologue's copy - re-read here it was a waited round trip
+        // ahead of the sweep; loading the label itself in the prologue measured -0.6 %: it
+        // delayed the x staging loads, profiles/r4_label)
+        const int im = img0 + slot;
+        if (im < B) label = c1.labels[c1.bi.row(im, bi_base)];
+        fcb = MRG ? __hip_atomic_load(dzo.fc_bias + o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : dzo.fc_bias[o];
       }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the partial-logit stores are out
+      const int im = img0 + (act ? slot : 0);
+      const int nblk = (im * HWi + HWi - 1) / CH - im * HWi / CH + 1;  // blocks touching image im
+      const gran_t* gr = (const gran_t*)dzo.gran;
+      const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+      bool dead = false;  // (wave-uniform) the bounded wait ran out: err is set, no more waiting
+      float a = 0.f;
       DDP_STAMP(STAMP_K_FWD_DZ, 1);
-      if (lane < nimg)
-        __hip_atomic_fetch_add(dzo.img_cnt + (img0 + lane) * FWD_DZ_CNT_STRIDE, 1, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-      store_a2();  // wave 0's a2 stores: after the drain above (it waited only for the partials)
-      {
-        const int im = img0 + (lane < nimg ? lane : 0);
-        const int kb0 = im * HWi / CH, kb1 = (im * HWi + HWi - 1) / CH;
-        const int want = kb1 - kb0 + 1;  // blocks touching image im
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-        while (true) {
-          const int v = lane < nimg ? __hip_atomic_load(dzo.img_cnt + im * FWD_DZ_CNT_STRIDE, __ATOMIC_RELAXED,
-                                                        __HIP_MEMORY_SCOPE_AGENT)
-                                    : want;
-          if (__all(v >= want)) break;
+      // terms [J0, J0 + DZ_SW) of xent_logit_acc's index sequence: every pass issues all the
+      // loads together and checks every tag; then the same adds in the same order
+      auto sweep = [&](auto j0c) {
+        constexpr int J0 = decltype(j0c)::value;
+        unsigned long long g[DZ_SW];
+#pragma unroll
+        for (int k = 0; k < DZ_SW; ++k) g[k] = 0;
+        // (no block of the wave's images has a term here: all are the +0.0f of a clamped index)
+        const bool none = J0 > 0 && !__any(act && nblk > J0);
+        while (!none) {
+          bool ok = true;
+          if (act) {
+#pragma unroll
+            for (int k = 0; k < DZ_SW; ++k)
+              g[k] = __hip_atomic_load(gr + xent_logit_idx(im, o, HWi, CH, NOF, J0 + k), __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+            for (int k = 0; k < DZ_SW; ++k) ok &= (unsigned)(g[k] >> 32) == dz_epoch;
+          }
+          if (__all(ok) || dead) break;
           if (__builtin_amdgcn_s_memrealtime() - t0 > FWD_DZ_WAIT_TICKS) {
             if (lane == 0 && dzo.err) __hip_atomic_store(dzo.err, 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            dead = true;
             break;
           }
           __builtin_amdgcn_s_sleep(1);
         }
-      }
+        a = xent_logit_acc_range<J0, J0 + DZ_SW>(a, im, o, HWi, CH, NOF, [&](int j, int) {
+          return __builtin_bit_cast(float, (unsigned)g[j - J0]);
+        });
+      };
+      sweep(std::integral_constant<int, 0>{});
+      if constexpr (DZ_SW < XENT_MAX_BLK) sweep(std::integral_constant<int, DZ_SW>{});
       DDP_STAMP(STAMP_K_FWD_DZ, 2);
-      if (lane < 2 * NOF) {
-        const int slot = lane >= NOF ? 1 : 0, o = lane - slot * NOF;
-        if (slot < nimg) {
-          const float a = xent_logit_acc(img0 + slot, o, HWi, CH, NOF, [&](int i) {
-            return __hip_atomic_load(fc_part + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          });
-          s_lg[lane] = (MRG ? __hip_atomic_load(dzo.fc_bias + o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                            : dzo.fc_bias[o]) + a;
-        }
-      }
+      asm volatile("" : "+v"(label));  // (keeps the label's clamp, and so its wait, behind the sweep)
+      if (act) s_lg[lane] = fcb + a;
       DDP_STAMP(STAMP_K_FWD_DZ, 4);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the row's logits (other lanes) are in LDS
-      if (lane < 2 * NOF) {
-        const int slot = lane >= NOF ? 1 : 0, o = lane - slot * NOF;
-        if (slot < nimg) {
-          float lossv = 0.f;
-          const float d = xent_row_dl(s_lg + slot * NOF, NOF, o, label, dzo.gscale, &lossv);
-          s_dl[lane] = d;
-          // the block holding the image's first pixel publishes its dL row and loss
-          if (dzo.dl_out && (slot == 1 || P0 == (long)img0 * HWi)) {
-            const int im = img0 + slot;
-            dzo.dl_out[im * NOF + o] = d;
-            if (o == 0) dzo.loss_rows[im] = lossv;
-          }
+      if (act) {
+        float lossv = 0.f;
+        const float d = xent_row_dl(s_lg + slot * NOF, NOF, o, label, dzo.gscale, &lossv);
+        s_dl[lane] = d;
+        // the block holding the image's first pixel publishes its dL row and loss
+        if (dzo.dl_out && (slot == 1 || P0 == (long)img0 * HWi)) {
+          dzo.dl_out[im * NOF + o] = d;
+          if (o == 0) dzo.loss_rows[im] = lossv;
         }
       }
     }

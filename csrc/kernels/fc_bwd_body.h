@@ -130,8 +130,15 @@ __device__ __forceinline__ void fc_bwd_bias_loss(const FcBwdExtras& ex, const fl
       if (last && ex.step_inc) *ex.step_inc = at + 1;  // ex.step_inc == ex.step_ctr (read just above)
     }
   }
-  if (ex.zero_i32 && (last || !ex.last_ctr))  // (block 0 when there is no last-block count)
-    for (int i = lane; i < ex.n_zero; i += 64) ex.zero_i32[(long)i * ex.zero_stride] = 0;
+  if (last || !ex.last_ctr) {  // (block 0 when there is no last-block count)
+    if (ex.zero_i32)
+      for (int i = lane; i < ex.n_zero; i += 64) ex.zero_i32[(long)i * ex.zero_stride] = 0;
+    // the level-3 forward's next launch tags its granules with the new generation + 1
+    if (ex.gen_inc && lane == 0) {
+      const unsigned g = *ex.gen_inc + 1u;
+      *ex.gen_inc = g == 0xffffffffu ? 0u : g;
+    }
+  }
 }
 
 // Wave-independent fc weight gradient (+ fused SGD) of 128 consecutive columns [col0,

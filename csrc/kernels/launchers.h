@@ -25,19 +25,25 @@ void conv1_wgrad(const void* x, bool x_is_u8, BatchIdx bi, const float* dy, cons
 // ---- 3x3 / s1 / p1 NHWC conv (MFMA) --------------------------------------------------
 // Fuse level 3 (bf16 SimpleCNN forward with the fc epilogue and the conv1 recompute): the
 // forward also produces dZ2 = relu2'(a2) * (dL . W_fc) for its own pixels, so the fc
-// backward leaves the critical path.  Every block publishes its partial logits
-// (write-through) and adds 1 to the arrival counter of each image it touches, waits until
-// every block of its image(s) has arrived, sums the image's logits in the fc_bwd prologue's
-// fixed order, evaluates the softmax cross-entropy gradient dL of its image(s) and then dZ2
-// from the bf16 fc weight fragments it already holds for the fc partials (fc_bwd's FMA
-// order: bit-identical dZ2).  All blocks must be co-resident (conv3x3_fwd_dz_fits).
-constexpr int FWD_DZ_CNT_STRIDE = 64;  // ints between two images' counters (256 B: no shared line)
+// backward leaves the critical path.  Every block publishes its partial logits as tagged
+// 8-byte granules {tag: high 32 bits, float bits: low 32 bits}, one aligned write-through
+// store each - the data is the flag: no drain, no counter.  Wave 0 then sweeps the granules
+// of every block of its image(s) until each carries this launch's tag, sums the image's
+// logits in the fc_bwd prologue's fixed order, evaluates the softmax cross-entropy gradient
+// dL of its image(s) and then dZ2 from the bf16 fc weight fragments it already holds for the
+// fc partials (fc_bwd's FMA order: bit-identical dZ2).  All blocks must be co-resident
+// (conv3x3_fwd_dz_fits).  The tag is *gen + 1 (0 skipped), read once at block entry; the
+// step's fc backward advances *gen (FcBwdExtras::gen_inc), so a granule left by any earlier
+// launch never matches.  A caller without the engine must likewise hand every launch on the
+// same granule buffer a *gen that differs from the previous launch's.
+constexpr int FWD_DZ_CNT_STRIDE = 64;  // ints between two images' counters of the inference
+                                       // kernel's tail (infer.hip; 256 B: no shared line)
 struct FwdDz {
   bf16_t* dz2 = nullptr;          // [B*H*W][Cout] out (write-through)
   float* dz2_f32 = nullptr;       // the same, exact-fp32 step
-  int* img_cnt = nullptr;         // [B][FWD_DZ_CNT_STRIDE] arrival counters (first int of each
-                                  // row), zero on entry (re-zeroed by the step's fc backward:
-                                  // FcBwdExtras::zero_i32)
+  unsigned long long* gran = nullptr;  // [blocks][2][10] granules, 8-byte aligned, zero before
+                                       // the first launch (blocks = conv3x3_dgrad_blocks at pxt)
+  const unsigned* gen = nullptr;  // the generation word (device memory), constant during a launch
   const float* fc_bias = nullptr;
   float gscale = 1.f;             // 1 / B (mean cross-entropy)
   int* err = nullptr;             // set to 3 when the wait times out (results invalid)
@@ -264,12 +270,14 @@ struct FcBwdExtras {
   // every block adds 1 to *last_ctr (zero on entry) when it is done - after its prologue read
   // the fc bias - and the block that arrives last writes dbias and the loss, applies the
   // fused SGD to the fc bias (p_b / m_b, when sgd.update), advances *step_inc (after reading
-  // the loss index from step_ctr) and zeroes zero_i32[0, n_zero) (the forward's per-image
-  // arrival counters, FwdDz::img_cnt).
+  // the loss index from step_ctr), advances *gen_inc (the level-3 forward's granule
+  // generation, FwdDz::gen: one thread, once per step) and zeroes zero_i32[0, n_zero)
+  // (dist_mode 4: the step head's two bucket-done counters).
   int* last_ctr = nullptr;
   float* p_b = nullptr;
   float* m_b = nullptr;
   int* step_inc = nullptr;
+  unsigned* gen_inc = nullptr;  // *gen_inc += 1, wrapping to 0 before 0xffffffff (tag = gen + 1 != 0)
   int* zero_i32 = nullptr;      // zero_i32[i * zero_stride] = 0 for i < n_zero
   int n_zero = 0, zero_stride = 1;
   int last_n = 0;               // arrivals of the last-block count (0: the grid size)

@@ -7,8 +7,9 @@
 // (EngineConfig::fuse_level 3, bf16, one GPU) is 2 kernels per step:
 //
 //   conv3x3_fwd   uint8 batch gather + /255 + conv1 (recomputed in the LDS staging pass)
-//                 + conv2 (MFMA) + bias + ReLU -> a2, the fc partial logits; then a
-//                 per-image in-launch wait for the image's other blocks, the softmax
+//                 + conv2 (MFMA) + bias + ReLU -> a2, the fc partial logits (published as
+//                 tagged 8-byte granules); then a per-image in-launch sweep of the image's
+//                 other blocks' granules, the softmax
 //                 cross-entropy dL and dZ2 = relu2'(a2) * (dL . W_fc) for its own pixels
 //   conv3x3_bwd   dgrad role (dZ1 + conv1 weight gradient), wgrad role (conv2 weight /
 //                 bias gradient slabs, two blocks per slab row), the fc role (fc weight
@@ -83,6 +84,15 @@ SimpleCNNEngine::SimpleCNNEngine(const EngineConfig& cfg, const EngineBuffers& b
     DDP_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&dev), err_host_, 0));
     b_.sync_err = dev;
   }
+  if (cfg_.fuse_level >= 3 && b_.sync_flags && b_.sync_err) {
+    // the level-3 forward's granules (pxt_fwd 1 has the most blocks) and generation word
+    const size_t ng = 2 * (size_t)cfg_.NO * (size_t)conv3x3_dgrad_blocks(cfg_.max_batch, cfg_.H, cfg_.W, 1);
+    DDP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&gran_), ng * sizeof(unsigned long long)));
+    DDP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&gen_), 256));
+    DDP_HIP_CHECK(hipMemset(gran_, 0, ng * sizeof(unsigned long long)));
+    DDP_HIP_CHECK(hipMemset(gen_, 0, 256));
+    DDP_HIP_CHECK(hipStreamSynchronize(nullptr));  // (the engine's streams do not order behind the null stream)
+  }
 }
 
 SimpleCNNEngine::~SimpleCNNEngine() {
@@ -94,6 +104,8 @@ SimpleCNNEngine::~SimpleCNNEngine() {
   for (hipEvent_t e : {e_b0_, e_b1_, e_d0_, e_d1_, e_fwd_, e_fc_}) hipEventDestroy(e);
   for (XarArgs& e : xar_cache_) hipFree(const_cast<XgmiArgs*>(e.dev));
   if (err_host_) hipHostFree(err_host_);
+  if (gran_) hipFree(gran_);
+  if (gen_) hipFree(gen_);
 }
 
 void SimpleCNNEngine::destroy_graph() {
@@ -199,7 +211,7 @@ void SimpleCNNEngine::launch_step(int B, int stride, bool first_momentum_step, u
     const int nsync = SYNC_RED_INTS + ((l3 || pair_mode) ? L3_FC_INTS : 0);
     c1.zero_i32 = b_.sync_flags;
     c1.zero_per_block = (nsync + nfwd - 1) / nfwd;
-    c1.zero_total = nsync;  // level 3: the per-image counters follow (L3_IMG_OFF)
+    c1.zero_total = nsync;
   }
   if (!l3 && plain_stale_) {
     // the plain bf16 fc shadow (read by the level-1 fc backward) was not refreshed by the
@@ -207,11 +219,12 @@ void SimpleCNNEngine::launch_step(int B, int stride, bool first_momentum_step, u
     refresh_shadows();
     plain_stale_ = false;
   }
-  // level 3: the forward also writes dZ2 (per-image in-launch wait for the logits)
+  // level 3: the forward also writes dZ2 (per-image in-launch sweep of the partial-logit granules)
   FwdDz dzo;
   if (l3) {
     dzo.dz2 = b_.dz2;
-    dzo.img_cnt = b_.sync_flags + L3_IMG_OFF;
+    dzo.gran = gran_;
+    dzo.gen = gen_;
     dzo.fc_bias = P + b_.off_bfc;
     dzo.gscale = 1.f / (float)B;
     dzo.err = b_.sync_err;
@@ -277,7 +290,7 @@ void SimpleCNNEngine::launch_step(int B, int stride, bool first_momentum_step, u
       late.count = 1;
     }
     BwdXar hx;
-    int* mc = b_.sync_flags + L3_IMG_OFF + (long)FWD_DZ_CNT_STRIDE * cfg_.max_batch;
+    int* mc = b_.sync_flags + L3_HEAD_OFF;
     if (cfg_.pxt_fwd == 1 && B == cfg_.max_batch) {
       if (!make_xar(hx, sa, M, sh_head)) throw std::runtime_error("engine: the step head needs the pair plan");
       hx.step_ctr = nullptr;  // (advanced by the fc role)
@@ -341,10 +354,12 @@ void SimpleCNNEngine::launch_step(int B, int stride, bool first_momentum_step, u
     // level 3: no dZ2 and no cross-entropy prologue here (the forward wrote dZ2, dL, losses)
     ex.part = nullptr;
     ex.loss_rows = b_.loss_rows;
-    ex.zero_i32 = dzo.img_cnt;  // re-arm the forward's per-image counters for the next step
-    // (dist_mode 4: and the step head's two bucket-done counters behind them)
-    ex.n_zero = ov ? cfg_.max_batch + 2 : B;
-    ex.zero_stride = FWD_DZ_CNT_STRIDE;
+    ex.gen_inc = gen_;  // the next forward's granule tags: a new generation
+    if (ov) {           // dist_mode 4: re-arm the step head's two bucket-done counters
+      ex.zero_i32 = b_.sync_flags + L3_HEAD_OFF;
+      ex.n_zero = 2;
+      ex.zero_stride = FWD_DZ_CNT_STRIDE;
+    }
     if (fc_role) {
       // inside the conv backward launch: block 0 of the fc role owns the fc bias, the loss
       // and the step counter (nothing else in the launch reads them)
@@ -548,7 +563,7 @@ bool SimpleCNNEngine::make_xar(BwdXar& xa, const SgdArgs& sa, float* M, const Sh
     dev = find(pair);
   }
   xa.args = dev;
-  // three counters of the step's zeroed hand-off words (the forward clears [0, L3_IMG_OFF))
+  // three counters of the step's zeroed hand-off words (the forward clears [0, L3_HEAD_OFF))
   xa.fc_done = b_.sync_flags + SYNC_RED_INTS + 8;
   xa.red_done = b_.sync_flags + SYNC_RED_INTS + 16;
   xa.xar_done = b_.sync_flags + SYNC_RED_INTS + 24;
@@ -614,7 +629,7 @@ void SimpleCNNEngine::join_buckets() {
 }
 
 // The exact-fp32 step: the bf16 chains on fp32 operands.  Level 3 (default): the forward
-// also computes dL and dZ2 (per-image in-launch wait), and one conv backward launch runs the
+// also computes dL and dZ2 (per-image in-launch granule sweep), and one conv backward launch runs the
 // dgrad and wgrad roles (both split over input-channel halves at two blocks per CU:
 // wgrad_split 2), the fc weight gradient + SGD as a third role (single process) and the
 // fused slab reduction + SGD.  Level 1: forward -> fc backward (cross-entropy prologue) ->
@@ -663,7 +678,8 @@ void SimpleCNNEngine::launch_step_f32(int B, int stride, bool first_momentum_ste
   FwdDz dzo;
   if (l3) {
     dzo.dz2_f32 = b_.dz2_f32;
-    dzo.img_cnt = b_.sync_flags + L3_IMG_OFF;
+    dzo.gran = gran_;
+    dzo.gen = gen_;
     dzo.fc_bias = P + b_.off_bfc;
     dzo.gscale = 1.f / (float)B;
     dzo.err = b_.sync_err;
@@ -677,7 +693,7 @@ void SimpleCNNEngine::launch_step_f32(int B, int stride, bool first_momentum_ste
                        conv3x3_bwd_fc_role_ok(H, W, C1, C2, cfg_.pxt_dgrad, cfg_.wgrad_split);
 
   // ---- forward: conv1 (recomputed) + conv2 + bias + ReLU -> a2, fused fc partial logits
-  //      (level 3: then dL and dZ2 after the per-image wait)
+  //      (level 3: then dL and dZ2 after the per-image granule sweep)
   conv3x3_fwd(static_cast<const float*>(nullptr), P + b_.off_w2, P + b_.off_b2, b_.a2_f32, B, H, W, C1, C2,
               true, b_.wfc_frag32, b_.fc_part, NO, cfg_.pxt_fwd, cs_, &c1, l3 ? &dzo : nullptr);
   // ---- loss + fc backward (bucket 0)
@@ -689,9 +705,7 @@ void SimpleCNNEngine::launch_step_f32(int B, int stride, bool first_momentum_ste
   ex.sys_store = use_x ? 1 : 0;
   if (l3) {
     ex.loss_rows = b_.loss_rows;  // dL and the row losses come from the forward
-    ex.zero_i32 = dzo.img_cnt;    // re-arm the forward's per-image counters
-    ex.n_zero = B;
-    ex.zero_stride = FWD_DZ_CNT_STRIDE;
+    ex.gen_inc = gen_;            // the next forward's granule tags: a new generation
   } else {
     ex.part = b_.fc_part;
     ex.HW = HW;

@@ -205,9 +205,9 @@ struct EngineBuffers {
   // in-launch hand-offs, zeroed by each step's forward (C1Src::zero_i32): [0, 256) the
   // fused conv backward's 8 arrival counters (32 ints apart), [256, 256 + fc blocks) the
   // level-2 dZ2 flags; level 3: [256] the fc backward's last-block counter (zeroed by the
-  // forward too) and [L3_IMG_OFF, + max_batch) the forward's per-image arrival counters
-  // (zeroed by the fc backward's last block); sync_err: wait-timeout word (0 = ok, 1 = dZ2
-  // wait, 2 = reduction, 3 = level-3 forward wait)
+  // forward too) and, dist_mode 4, [L3_HEAD_OFF, + 2 * FWD_DZ_CNT_STRIDE) the step head's two
+  // bucket-done counters (zeroed by the fc backward's last block); sync_err: wait-timeout
+  // word (0 = ok, 1 = dZ2 wait, 2 = reduction, 3 = level-3 forward's granule sweep)
   int* sync_flags = nullptr;
   int* sync_err = nullptr;
   // data
@@ -218,7 +218,7 @@ struct EngineBuffers {
 };
 
 constexpr int L3_FC_INTS = 32;                          // [SYNC_RED_INTS, + 32): fc last-block counter
-constexpr int L3_IMG_OFF = SYNC_RED_INTS + L3_FC_INTS;  // per-image arrival counters
+constexpr int L3_HEAD_OFF = SYNC_RED_INTS + L3_FC_INTS;  // dist_mode 4: the two bucket-done counters
 
 struct EngineConfig {
   int max_batch, H, W, C1, C2, NO;
@@ -234,7 +234,7 @@ struct EngineConfig {
   // (2: a level-1 variant with fc_bwd and the conv backward in one launch - measured
   //    slower than level 1 and removed in round 4)
   // 3: the fc backward leaves the critical path - the conv forward computes dZ2 itself
-  //    (FwdDz: per-image in-launch wait, then dL and dZ2 from the fc weight fragments it
+  //    (FwdDz: per-image in-launch granule sweep, then dL and dZ2 from the fc weight fragments it
   //    holds) and the fc weight gradient + fused SGD (fc_bwd without dX, dL given) runs as
   //    a third role of the conv backward launch (single process, l3_fc_role: 2 kernels per
   //    step), or as a light kernel between the two (world size > 1: the fc bucket's
@@ -316,7 +316,7 @@ class SimpleCNNEngine {
   hipStream_t stream() const { return cs_; }
   void synchronize();  // throws if a level-2 hand-off wait timed out
   // in-launch wait-timeout word (0 = ok, 1 = level-2 dZ2 wait, 2 = fused reduction,
-  // 3 = level-3 forward's per-image wait); sticky
+  // 3 = level-3 forward's granule sweep); sticky
   int sync_error() const { return err_host_ ? __atomic_load_n(err_host_, __ATOMIC_ACQUIRE) : 0; }
   // whether a step of `batch` images runs the level-3 chain (fuse_level 3 and it applies)
   bool level3_active(int batch);
@@ -406,6 +406,12 @@ class SimpleCNNEngine {
   hipStream_t xs_ = nullptr;        // ... and the stream their copies run on
   bool plain_stale_ = false;  // level-3 steps skipped the plain bf16 fc shadow
   int* err_host_ = nullptr;  // coherent host word behind b_.sync_err
+  // level 3 (launchers.h FwdDz): the forward's partial-logit granules - [blocks][2][NO] 8-byte
+  // {tag, float bits} words, an allocation of their own sized for max_batch at pxt_fwd 1,
+  // zeroed once here - and the generation word the tags derive from (advanced once per step
+  // by the fc backward; never restarted, unlike step_ctr, so no tag ever recurs)
+  unsigned long long* gran_ = nullptr;
+  unsigned* gen_ = nullptr;
 };
 
 }  // namespace ddp_amd

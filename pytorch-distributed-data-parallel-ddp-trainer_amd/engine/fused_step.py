@@ -331,12 +331,12 @@ class FusedSimpleCNNEngine:
                     else data.labels_i32),
             idx=torch.zeros(n_rank, dtype=torch.int32, device=dev),
         )
-        # in-launch hand-offs (fused slab reduction, level-3 arrival counters), zeroed by each
-        # step's forward, and their wait-timeout word
-        # (level 3: [256] the fc side kernel's last-block counter, [288, 288 + B) the
-        # forward's per-image arrival counters - engine.cpp L3_IMG_OFF)
-        # (+ 2 rows: dist_mode 4's bucket-done counters behind the image counters)
-        nfl = 256 + 32 + 64 * (B + 2)  # (counters 64 ints apart: FWD_DZ_CNT_STRIDE)
+        # in-launch hand-offs (fused slab reduction), zeroed by each step's forward, and their
+        # wait-timeout word
+        # (level 3: [256] the fc side kernel's last-block counter, [288, 288 + 2 * 64) dist_mode
+        # 4's two bucket-done counters - runtime.h L3_HEAD_OFF; the level-3 forward's partial-logit
+        # granules and their generation word are the native engine's own allocations)
+        nfl = 256 + 32 + 64 * 2  # (counters 64 ints apart: FWD_DZ_CNT_STRIDE)
         self.t["sync_flags"] = torch.zeros(nfl, dtype=torch.int32, device=dev)
         # (the engine replaces it by a coherent host word: eng.sync_error)
         self.t["sync_err"] = torch.zeros(1, dtype=torch.int32, device=dev)
