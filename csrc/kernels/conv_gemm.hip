@@ -29,6 +29,7 @@
 #include <type_traits>
 
 #include "kernels/common.h"
+#include "kernels/conv_infer.h"
 #include "kernels/launchers.h"
 
 namespace ddp_amd {
@@ -69,16 +70,48 @@ inline bool stem_geo_224(const ConvGeom& g) {
 }
 #define SG_(f, rt) (StemGeo<SG>::f ? StemGeo<SG>::f : (rt))
 
+// Inference epilogue of the 2 x 2-wave MFMA tiling: accumulator (i, j) holds output channels
+// co + 16 i .. + 3 of pixel px + 16 j.  relu?(acc * sc + sh (+ res)) rounded to bf16 once;
+// the residual is one 8-byte load beside the 8-byte store.
+template <int TCO, int TPX, bool RELU>
+__device__ __forceinline__ void infer_epilogue(const f32x4 (&acc)[TCO][TPX], const float4* isc, const float4* ish,
+                                               const bf16_t* __restrict__ res, bf16_t* __restrict__ Y, int Cout,
+                                               int Ptot, int px, int co) {
+#pragma unroll
+  for (int j = 0; j < TPX; ++j) {
+    const int Pj = px + 16 * j;
+    if (Pj >= Ptot) continue;
+#pragma unroll
+    for (int i = 0; i < TCO; ++i) {
+      const long off = (long)Pj * Cout + co + 16 * i;
+      const float sc[4] = {isc[i].x, isc[i].y, isc[i].z, isc[i].w};
+      const float sh[4] = {ish[i].x, ish[i].y, ish[i].z, ish[i].w};
+      float v[4], rv[4] = {0.f, 0.f, 0.f, 0.f};
+      if (res) unpack4(*reinterpret_cast<const uint2*>(res + off), rv);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        v[r] = fmaf(acc[i][j][r], sc[r], sh[r]);
+        if (res) v[r] += rv[r];
+        if (RELU) v[r] = fmaxf(v[r], 0.f);
+      }
+      *reinterpret_cast<uint2*>(Y + off) = pack4(v[0], v[1], v[2], v[3]);
+    }
+  }
+}
+
 // STEM: Cin == 4 (3 real channels + 1 zero pad); a K-step covers 8 taps x 4 channels,
 // k = tap*4 + c, so the weight row [KH*KW*4] is still contiguous per K-step.
-template <int BP, int BC, bool RELU, bool STATS, bool STEM, bool PART, int SG = 0>
+// INF: the inference epilogue (conv_infer.h InferEpi `ie`, unused otherwise) instead of bias /
+// statistics.
+template <int BP, int BC, bool RELU, bool STATS, bool STEM, bool PART, int SG = 0, bool INF = false>
 __global__ __launch_bounds__(256) void conv_gemm_fwd_kernel(ConvGeom g, const bf16_t* __restrict__ X,
                                                             const bf16_t* __restrict__ Wt,
                                                             const float* __restrict__ bias,
                                                             bf16_t* __restrict__ Y,
                                                             float* __restrict__ stats,
-                                                            float* __restrict__ part, int ks_per) {
+                                                            float* __restrict__ part, int ks_per, InferEpi ie) {
   static_assert(!STEM || (BP == 128 && !PART), "stem: 128-pixel tile, unsplit");
+  static_assert(!INF || (!STATS && !PART), "inference epilogue: unsplit, no statistics");
   __shared__ __attribute__((aligned(16))) bf16_t sA[2][BC * CG_RS];
   __shared__ __attribute__((aligned(16))) bf16_t sB[2][BP * CG_RS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -181,6 +214,17 @@ __global__ __launch_bounds__(256) void conv_gemm_fwd_kernel(ConvGeom g, const bf
   for (int u = 0; u < CG_PIPE; ++u)
     if (kb + u < ke) load_k(kb + u, ra[u], rb[u]);
   if (kb < ke) store_k(0, ra[0], rb[0]);
+  // INF: the lane's 4 consecutive output channels of each tile row, requested here so that
+  // they land during the K loop
+  float4 isc[INF ? TCO : 1], ish[INF ? TCO : 1];
+  if constexpr (INF) {
+#pragma unroll
+    for (int i = 0; i < TCO; ++i) {
+      const int co = co0 + wco * (BC / 2) + 16 * i + 4 * (lane >> 4);
+      isc[i] = *reinterpret_cast<const float4*>(ie.sc + co);
+      ish[i] = *reinterpret_cast<const float4*>(ie.sh + co);
+    }
+  }
   __syncthreads();
   const int kofs = 8 * (lane >> 4), col = lane & 15;
   for (int base = kb; base < ke; base += CG_PIPE) {
@@ -220,6 +264,11 @@ __global__ __launch_bounds__(256) void conv_gemm_fwd_kernel(ConvGeom g, const bf
             make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
       }
     }
+    return;
+  }
+  if constexpr (INF) {
+    infer_epilogue<TCO, TPX, RELU>(acc, isc, ish, ie.res, Y, g.Cout, Ptot, p0 + wpx * (BP / 2) + col,
+                                   co0 + wco * (BC / 2) + 4 * (lane >> 4));
     return;
   }
   float csum[TCO][4], csq[TCO][4];
@@ -290,12 +339,14 @@ __global__ __launch_bounds__(256) void conv_gemm_fwd_kernel(ConvGeom g, const bf
 // lane's 8 K values are taps 2q, 2q+1 of one input row = 2 adjacent pixels x 4 channels =
 // 16 contiguous bytes of the staged row (LDS column j = iw + 3, even for every read).
 constexpr int STEM_ROWS = 11, STEM_COLS = 232;  // staged input rows / columns (j = iw + 3)
-template <bool RELU, bool STATS>
+template <bool RELU, bool STATS, bool INF = false>  // INF: see conv_gemm_fwd_kernel
 __global__ __launch_bounds__(256, 2) void conv_stem_halo_fwd_kernel(ConvGeom g, const bf16_t* __restrict__ X,
                                                                  const bf16_t* __restrict__ Wt,
                                                                  const float* __restrict__ bias,
                                                                  bf16_t* __restrict__ Y,
-                                                                 float* __restrict__ stats, int ntiles) {
+                                                                 float* __restrict__ stats, int ntiles,
+                                                                 InferEpi ie) {
+  static_assert(!INF || !STATS, "inference epilogue: no statistics");
   using SGeo = StemGeo<1>;
   constexpr int BP = 128, BC = 64, TCO = 2, TPX = 4;
   constexpr int OHW = SGeo::OH * SGeo::OW, KWC = 49 * 4, RS = STEM_COLS * 4;  // RS: elements per row
@@ -323,6 +374,15 @@ __global__ __launch_bounds__(256, 2) void conv_stem_halo_fwd_kernel(ConvGeom g, 
       const uint2 t0 = *reinterpret_cast<const uint2*>(wr + (kh * 7 + 2 * q) * 4);
       const uint2 t1 = q < 3 ? *reinterpret_cast<const uint2*>(wr + (kh * 7 + 2 * q + 1) * 4) : make_uint2(0u, 0u);
       a[kh][i] = __builtin_bit_cast(bf16x8, make_uint4(t0.x, t0.y, t1.x, t1.y));
+    }
+  }
+  float4 isc[INF ? TCO : 1], ish[INF ? TCO : 1];  // the block's channels: once, like the weights
+  if constexpr (INF) {
+#pragma unroll
+    for (int i = 0; i < TCO; ++i) {
+      const int co = co0 + wco * (BC / 2) + 16 * i + 4 * (lane >> 4);
+      isc[i] = *reinterpret_cast<const float4*>(ie.sc + co);
+      ish[i] = *reinterpret_cast<const float4*>(ie.sh + co);
     }
   }
   // the zero columns of both buffers: j = 0..2 (iw = -3..-1) and j = 227..231 (iw >= 224)
@@ -400,8 +460,11 @@ __global__ __launch_bounds__(256, 2) void conv_stem_halo_fwd_kernel(ConvGeom g, 
     for (int i = 0; i < TCO; ++i)
 #pragma unroll
       for (int r = 0; r < 4; ++r) csum[i][r] = csq[i][r] = 0.f;
+    if constexpr (INF)
+      infer_epilogue<TCO, TPX, RELU>(acc, isc, ish, ie.res, Y, g.Cout, Ptot, p0 + wpx * (BP / 2) + col,
+                                     co0 + wco * (BC / 2) + 4 * (lane >> 4));
 #pragma unroll
-    for (int j = 0; j < TPX; ++j) {
+    for (int j = 0; j < (INF ? 0 : TPX); ++j) {
       const int Pj = p0 + wpx * (BP / 2) + 16 * j + col;
       const bool ok = Pj < Ptot;
 #pragma unroll
@@ -629,12 +692,14 @@ __global__ __launch_bounds__(256) void conv_gemm_dgrad_kernel(ConvGeom g, const 
 // by Xact (> 0) and optional per-block BatchNorm partials [gridDim.x][2][C] (sum, sum of
 // squares of the stored bf16 values).  Thread = 8 channels of one pixel; block = C/8
 // channel groups x 256/(C/8) pixel lanes over `rpb` pixels.
-template <bool MASK, bool STATS>
+// INF: the inference epilogue on the fp32 sum (relu?(sum * sc + sh (+ res)), one rounding)
+template <bool MASK, bool STATS, bool INF = false>
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ part, int S, int P,
                                                             int C, int rpb,
                                                             const bf16_t* __restrict__ Xact,
                                                             bf16_t* __restrict__ out,
-                                                            float* __restrict__ stats) {
+                                                            float* __restrict__ stats, InferEpi ie) {
+  static_assert(!INF || (!MASK && !STATS), "inference epilogue: no mask, no statistics");
   extern __shared__ __attribute__((aligned(16))) float sred[];  // [pl][2][C]
   const int cg = C / 8, pl = 256 / cg;
   const int tg = threadIdx.x % cg, tp = threadIdx.x / cg;
@@ -643,6 +708,16 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 #pragma unroll
   for (int j = 0; j < 8; ++j) s[j] = q[j] = 0.f;
   const int p0 = blockIdx.x * rpb, p1 = min(P, p0 + rpb);
+  float isc[8], ish[8];  // INF: this thread's 8 channels
+  if constexpr (INF) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const float4 a = *reinterpret_cast<const float4*>(ie.sc + tg * 8 + 4 * h);
+      const float4 b = *reinterpret_cast<const float4*>(ie.sh + tg * 8 + 4 * h);
+      isc[4 * h] = a.x; isc[4 * h + 1] = a.y; isc[4 * h + 2] = a.z; isc[4 * h + 3] = a.w;
+      ish[4 * h] = b.x; ish[4 * h + 1] = b.y; ish[4 * h + 2] = b.z; ish[4 * h + 3] = b.w;
+    }
+  }
   for (int p = p0 + tp; p < p1; p += pl) {
     const long off = (long)p * C + tg * 8;
     float v[8];
@@ -663,6 +738,20 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
       unpack4(make_uint2(xm.z, xm.w), x + 4);
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = x[j] > 0.f ? v[j] : 0.f;
+    }
+    if constexpr (INF) {
+      float rv[8];
+      if (ie.res) {
+        const uint4 rr = *reinterpret_cast<const uint4*>(ie.res + off);
+        unpack4(make_uint2(rr.x, rr.y), rv);
+        unpack4(make_uint2(rr.z, rr.w), rv + 4);
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        v[j] = fmaf(v[j], isc[j], ish[j]);
+        if (ie.res) v[j] += rv[j];
+        if (ie.relu) v[j] = fmaxf(v[j], 0.f);
+      }
     }
     const uint2 lo = pack4(v[0], v[1], v[2], v[3]), hi = pack4(v[4], v[5], v[6], v[7]);
     *reinterpret_cast<uint4*>(out + off) = make_uint4(lo.x, lo.y, hi.x, hi.y);
@@ -988,7 +1077,7 @@ static void splitk_reduce(const float* part, int S, long P, int C, const bf16_t*
   int rpb;
   const int nb = splitk_rows(P, C, &rpb);
   const size_t lds = stats ? sizeof(float) * (256 / (C / 8)) * 2 * C : 0;
-#define SKR(M, ST) hipLaunchKernelGGL((splitk_reduce_kernel<M, ST>), dim3(nb), dim3(256), lds, s, part, S, (int)P, C, rpb, Xact, out, stats)
+#define SKR(M, ST) hipLaunchKernelGGL((splitk_reduce_kernel<M, ST>), dim3(nb), dim3(256), lds, s, part, S, (int)P, C, rpb, Xact, out, stats, InferEpi{})
   if (Xact) { if (stats) SKR(true, true); else SKR(true, false); }
   else { if (stats) SKR(false, true); else SKR(false, false); }
 #undef SKR
@@ -1019,7 +1108,7 @@ void conv_gemm_fwd(const ConvGeom& g, const ConvPlan& pl, const bf16_t* X, const
       }();
       const int ntiles = (int)grid.x;
       const dim3 sg(std::min(ntiles, 2 * cus), grid.y, 1);
-#define CSH(RL, ST) hipLaunchKernelGGL((conv_stem_halo_fwd_kernel<RL, ST>), sg, dim3(256), 0, s, g, X, Wt, bias, Y, stats, ntiles)
+#define CSH(RL, ST) hipLaunchKernelGGL((conv_stem_halo_fwd_kernel<RL, ST>), sg, dim3(256), 0, s, g, X, Wt, bias, Y, stats, ntiles, InferEpi{})
       if (stats) CSH(false, true);
       else if (relu) CSH(true, false);
       else CSH(false, false);
@@ -1028,8 +1117,8 @@ void conv_gemm_fwd(const ConvGeom& g, const ConvPlan& pl, const bf16_t* X, const
     }
 #define CGS(RL, ST)                                                                                                  \
   do {                                                                                                               \
-    if (s224) hipLaunchKernelGGL((conv_gemm_fwd_kernel<128, 64, RL, ST, true, false, 1>), grid, dim3(256), 0, s, g, X, Wt, bias, Y, stats, part, kp); \
-    else hipLaunchKernelGGL((conv_gemm_fwd_kernel<128, 64, RL, ST, true, false, 0>), grid, dim3(256), 0, s, g, X, Wt, bias, Y, stats, part, kp); \
+    if (s224) hipLaunchKernelGGL((conv_gemm_fwd_kernel<128, 64, RL, ST, true, false, 1>), grid, dim3(256), 0, s, g, X, Wt, bias, Y, stats, part, kp, InferEpi{}); \
+    else hipLaunchKernelGGL((conv_gemm_fwd_kernel<128, 64, RL, ST, true, false, 0>), grid, dim3(256), 0, s, g, X, Wt, bias, Y, stats, part, kp, InferEpi{}); \
   } while (0)
     if (stats) CGS(false, true);
     else if (relu) CGS(true, false);
@@ -1037,7 +1126,7 @@ void conv_gemm_fwd(const ConvGeom& g, const ConvPlan& pl, const bf16_t* X, const
 #undef CGS
     return;
   }
-#define CGF(BP, BC, RL, ST, PT) hipLaunchKernelGGL((conv_gemm_fwd_kernel<BP, BC, RL, ST, false, PT>), grid, dim3(256), 0, s, g, X, Wt, bias, Y, stats, part, kp)
+#define CGF(BP, BC, RL, ST, PT) hipLaunchKernelGGL((conv_gemm_fwd_kernel<BP, BC, RL, ST, false, PT>), grid, dim3(256), 0, s, g, X, Wt, bias, Y, stats, part, kp, InferEpi{})
 #define CGF_BP(BP, BC)                                                           \
   if (pl.splits > 1) CGF(BP, BC, false, false, true);                            \
   else if (stats) { if (relu) CGF(BP, BC, true, true, false); else CGF(BP, BC, false, true, false); } \
@@ -1050,6 +1139,67 @@ void conv_gemm_fwd(const ConvGeom& g, const ConvPlan& pl, const bf16_t* X, const
     // bias / ReLU of the split path: only the BatchNorm use (no bias, no ReLU) is split
     splitk_reduce(part, pl.splits, (long)g.N * g.OH * g.OW, g.Cout, nullptr, Y, stats, s);
   }
+}
+
+// Inference forward: the same plans and K-loop kernels; split plans reuse the training PART
+// kernels and finish in splitk_reduce_kernel's INF build.
+void conv_gemm_infer(const ConvGeom& g, const ConvPlan& pl, const bf16_t* X, const bf16_t* Wt,
+                     const InferEpi& ie, bf16_t* Y, float* part, hipStream_t s) {
+  if (!ie.sc || !ie.sh) throw std::runtime_error("conv_gemm_infer: the folded BatchNorm vectors are required");
+  if (pl.splits > 1 && !part) throw std::runtime_error("conv_gemm_infer: split plan needs the fp32 workspace");
+  const long P = (long)g.N * g.OH * g.OW;
+  const float* nobias = nullptr;
+  float* nof = nullptr;
+  auto reduce = [&] {
+    int rpb;
+    const int nb = splitk_rows(P, g.Cout, &rpb);
+    hipLaunchKernelGGL((splitk_reduce_kernel<false, false, true>), dim3(nb), dim3(256), 0, s, part, pl.splits, (int)P,
+                       g.Cout, rpb, (const bf16_t*)nullptr, Y, (float*)nullptr, ie);
+  };
+  if (pl.halo) {
+    conv_halo_infer(g, pl.bp, pl.bc, pl.splits, X, Wt, ie, Y, part, s);
+    if (pl.splits > 1) reduce();
+    return;
+  }
+  const dim3 grid(pl.grid_x, pl.grid_y, pl.splits);
+  const int kp = pl.ks_per;
+  const bool relu = ie.relu != 0;
+  if (g.Cin == 4) {  // stem (never split): the same kernel choice as conv_gemm_fwd
+    const bool s224 = stem_geo_224(g);
+    static const int stem_halo = [] { const char* e = getenv("DDP_AMD_STEM_HALO"); return e ? atoi(e) : 1; }();
+    if (s224 && stem_halo && pl.splits <= 1 && grid.x * 128 >= (unsigned)(g.N * 112 * 112)) {
+      static const int cus = [] {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256;
+        return n > 0 ? n : 256;
+      }();
+      const int ntiles = (int)grid.x;
+      const dim3 sg(std::min(ntiles, 2 * cus), grid.y, 1);
+#define CSI(RL) hipLaunchKernelGGL((conv_stem_halo_fwd_kernel<RL, false, true>), sg, dim3(256), 0, s, g, X, Wt, nobias, Y, nof, ntiles, ie)
+      if (relu) CSI(true); else CSI(false);
+#undef CSI
+      return;
+    }
+#define CGI_S(RL, SGV) hipLaunchKernelGGL((conv_gemm_fwd_kernel<128, 64, RL, false, true, false, SGV, true>), grid, dim3(256), 0, s, g, X, Wt, nobias, Y, nof, nof, kp, ie)
+    if (s224) { if (relu) CGI_S(true, 1); else CGI_S(false, 1); }
+    else { if (relu) CGI_S(true, 0); else CGI_S(false, 0); }
+#undef CGI_S
+    return;
+  }
+  if (pl.splits > 1) {
+#define CGP(BP, BC) hipLaunchKernelGGL((conv_gemm_fwd_kernel<BP, BC, false, false, false, true>), grid, dim3(256), 0, s, g, X, Wt, nobias, Y, nof, part, kp, InferEpi{})
+    if (pl.bp == 128) { if (pl.bc == 128) CGP(128, 128); else CGP(128, 64); }
+    else { if (pl.bc == 128) CGP(64, 128); else CGP(64, 64); }
+#undef CGP
+    reduce();
+    return;
+  }
+#define CGI_K(BP, BC, RL) hipLaunchKernelGGL((conv_gemm_fwd_kernel<BP, BC, RL, false, false, false, 0, true>), grid, dim3(256), 0, s, g, X, Wt, nobias, Y, nof, nof, kp, ie)
+#define CGI(BP, BC) do { if (relu) CGI_K(BP, BC, true); else CGI_K(BP, BC, false); } while (0)
+  if (pl.bp == 128) { if (pl.bc == 128) CGI(128, 128); else CGI(128, 64); }
+  else { if (pl.bc == 128) CGI(64, 128); else CGI(64, 64); }
+#undef CGI
+#undef CGI_K
 }
 
 void conv_gemm_dgrad(const ConvGeom& g, const ConvPlan& pl, const bf16_t* dY, const bf16_t* W,

@@ -18,6 +18,7 @@
 
 #include "kernels/bn_affine.h"
 #include "kernels/common.h"
+#include "kernels/conv_infer.h"
 #include "kernels/launchers.h"
 
 namespace ddp_amd {
@@ -33,13 +34,16 @@ constexpr int HL_MAXPX = 232;     // largest halo: (R+2) x (W+2) = 4 x 58 at W =
 // GW: the image width as a template constant (56 / 28 / 14 for ResNet-18's layers; 0 =
 // runtime) - the halo index divisions and the tap offsets then fold (the per-dispatch SQ
 // counters showed ~10 VALU instructions per MFMA in this kernel, profiles/r4_resnet/pmc)
-template <int BC, int BP, bool STATS, bool PART, bool AFF = false, int GW = 0>
+// INF: the inference epilogue (conv_infer.h InferEpi `ie`, unused otherwise: relu?(acc * sc +
+// sh (+ res)), one rounding) instead of the raw store / statistics.
+template <int BC, int BP, bool STATS, bool PART, bool AFF = false, int GW = 0, bool INF = false>
 __global__ __launch_bounds__(256) void conv3x3s1_halo_fwd_kernel(ConvGeom g, const bf16_t* __restrict__ X,
                                                                  const bf16_t* __restrict__ Wt,
                                                                  bf16_t* __restrict__ Y,
                                                                  float* __restrict__ stats,
                                                                  float* __restrict__ part, int R,
-                                                                 int chunks_per_split, BnAffine bn) {
+                                                                 int chunks_per_split, BnAffine bn, InferEpi ie) {
+  static_assert(!INF || (!STATS && !PART && !AFF), "inference epilogue: unsplit, no statistics, materialised input");
   constexpr int TCO = BC / 32, TPX = BP / 32;
   constexpr int HCH = (HL_MAXPX * 4 + 255) / 256;  // 16-B halo chunks per thread
   // weights of one kernel row (3 taps) per K-step: 3 MFMA K-steps between barriers
@@ -141,6 +145,16 @@ __global__ __launch_bounds__(256) void conv3x3s1_halo_fwd_kernel(ConvGeom g, con
     store_halo(0, rh, c_beg);
     store_w(0, ra);
   }
+  // INF: the lane's 4 consecutive output channels per tile row, in flight during the K loop
+  float4 isc[INF ? TCO : 1], ish[INF ? TCO : 1];
+  if constexpr (INF) {
+#pragma unroll
+    for (int i = 0; i < TCO; ++i) {
+      const int co = co0 + wco * (BC / 2) + 16 * i + 4 * (lane >> 4);
+      isc[i] = *reinterpret_cast<const float4*>(ie.sc + co);
+      ish[i] = *reinterpret_cast<const float4*>(ie.sh + co);
+    }
+  }
   __syncthreads();
   int step = 0;
   for (int ch = c_beg; ch < c_end; ++ch) {
@@ -194,6 +208,22 @@ __global__ __launch_bounds__(256) void conv3x3s1_halo_fwd_kernel(ConvGeom g, con
         if (ok)
           *reinterpret_cast<float4*>(part + ((long)bk.z * Ptot + P) * g.Cout + co) =
               make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
+        continue;
+      }
+      if constexpr (INF) {
+        if (ok) {
+          const float sc[4] = {isc[i].x, isc[i].y, isc[i].z, isc[i].w};
+          const float sh[4] = {ish[i].x, ish[i].y, ish[i].z, ish[i].w};
+          float v[4], rv[4] = {0.f, 0.f, 0.f, 0.f};
+          if (ie.res) unpack4(*reinterpret_cast<const uint2*>(ie.res + P * g.Cout + co), rv);
+#pragma unroll
+          for (int rr = 0; rr < 4; ++rr) {
+            v[rr] = fmaf(acc[i][j][rr], sc[rr], sh[rr]);
+            if (ie.res) v[rr] += rv[rr];
+            if (ie.relu) v[rr] = fmaxf(v[rr], 0.f);
+          }
+          *reinterpret_cast<uint2*>(Y + P * g.Cout + co) = pack4(v[0], v[1], v[2], v[3]);
+        }
         continue;
       }
       const uint2 pk = pack4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
@@ -455,8 +485,8 @@ void conv_halo_fwd(const ConvGeom& g, int bp, int bc, int splits, const bf16_t* 
   const int gw = g.W == 56 ? 56 : g.W == 28 ? 28 : g.W == 14 ? 14 : 0;
 #define HLF_W(BC, BP, ST, PT, GWV)                                                                              \
   do {                                                                                                          \
-    if (af) hipLaunchKernelGGL((conv3x3s1_halo_fwd_kernel<BC, BP, ST, PT, true, GWV>), grid, dim3(256), 0, s, g, X, Wt, Y, stats, part, R, cps, a); \
-    else hipLaunchKernelGGL((conv3x3s1_halo_fwd_kernel<BC, BP, ST, PT, false, GWV>), grid, dim3(256), 0, s, g, X, Wt, Y, stats, part, R, cps, a); \
+    if (af) hipLaunchKernelGGL((conv3x3s1_halo_fwd_kernel<BC, BP, ST, PT, true, GWV>), grid, dim3(256), 0, s, g, X, Wt, Y, stats, part, R, cps, a, InferEpi{}); \
+    else hipLaunchKernelGGL((conv3x3s1_halo_fwd_kernel<BC, BP, ST, PT, false, GWV>), grid, dim3(256), 0, s, g, X, Wt, Y, stats, part, R, cps, a, InferEpi{}); \
   } while (0)
 #define HLF(BC, BP, ST, PT)                                              \
   do {                                                                   \
@@ -474,6 +504,36 @@ void conv_halo_fwd(const ConvGeom& g, int bp, int bc, int splits, const bf16_t* 
 #undef HLF_BP
 #undef HLF
 #undef HLF_W
+}
+
+// Inference: the non-AFF build with the affine / residual / ReLU epilogue; split plans run
+// the training PART kernel (the caller finishes in the inference split-K reduction).
+void conv_halo_infer(const ConvGeom& g, int bp, int bc, int splits, const bf16_t* X, const bf16_t* Wt,
+                     const InferEpi& ie, bf16_t* Y, float* part, hipStream_t s) {
+  if (splits > 1) {
+    conv_halo_fwd(g, bp, bc, splits, X, Wt, Y, nullptr, part, s, nullptr);
+    return;
+  }
+  const int R = conv_halo_rows(g, bp);
+  const int RG = (g.H + R - 1) / R;
+  const int nch = g.Cin / HL_KS;
+  const dim3 grid(g.N * RG, g.Cout / bc, 1);
+  const int gw = g.W == 56 ? 56 : g.W == 28 ? 28 : g.W == 14 ? 14 : 0;  // (see conv_halo_fwd)
+  float* nof = nullptr;
+#define HLI_W(BC, BP, GWV)                                                                                        \
+  hipLaunchKernelGGL((conv3x3s1_halo_fwd_kernel<BC, BP, false, false, false, GWV, true>), grid, dim3(256), 0, s, g, X, \
+                     Wt, Y, nof, nof, R, nch, BnAffine{}, ie)
+#define HLI(BC, BP)                                          \
+  do {                                                       \
+    if (BC != 64 || gw == 0) HLI_W(BC, BP, 0);               \
+    else if (gw == 56) HLI_W(BC, BP, (BC == 64 ? 56 : 0));   \
+    else if (gw == 28) HLI_W(BC, BP, (BC == 64 ? 28 : 0));   \
+    else HLI_W(BC, BP, (BC == 64 ? 14 : 0));                 \
+  } while (0)
+  if (bp == 128) { if (bc == 128) HLI(128, 128); else HLI(64, 128); }
+  else { if (bc == 128) HLI(128, 64); else HLI(64, 64); }
+#undef HLI
+#undef HLI_W
 }
 
 

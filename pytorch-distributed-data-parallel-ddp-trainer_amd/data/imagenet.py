@@ -31,6 +31,24 @@ def synthetic_imagenet(n: int = 2048, size: int = 224, num_classes: int = 1000, 
     return imgs, labels
 
 
+def synthetic_imagenet_test(n: int, size: int = 224, num_classes: int = 1000, seed: int = 0, n_train: int = 2048):
+    """The synthetic held-out split: ``(uint8 [n, size, size, 3], int64 [n])`` in the SAME class
+    colours as ``synthetic_imagenet(n_train, size, num_classes, seed)`` (that generator is
+    replayed up to its colour draw), labels and noise from a generator of its own - so the
+    split is deterministic and no test image repeats a train image."""
+    g = torch.Generator().manual_seed(seed)
+    torch.randint(0, num_classes, (n_train,), generator=g)  # the train labels' draw
+    colours = torch.randint(32, 224, (num_classes, 3), generator=g, dtype=torch.int16)
+    gt = torch.Generator().manual_seed(0x7E57 + 1000003 * seed)
+    labels = torch.randint(0, num_classes, (n,), generator=gt)
+    imgs = torch.empty(n, size, size, 3, dtype=torch.uint8)
+    for s in range(0, n, 64):  # bounded temporaries
+        e = min(n, s + 64)
+        noise = torch.randint(-32, 33, (e - s, size, size, 3), generator=gt, dtype=torch.int16)
+        imgs[s:e] = (colours[labels[s:e]].view(-1, 1, 1, 3) + noise).clamp_(0, 255).to(torch.uint8)
+    return imgs, labels
+
+
 class DeviceImages:
     """uint8 NHWC images + int64 labels resident on one device."""
 

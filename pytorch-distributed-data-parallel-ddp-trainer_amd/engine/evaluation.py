@@ -1,4 +1,5 @@
-"""Held-out evaluation: accuracy and mean loss of SimpleCNN over a ``DeviceMNIST`` split.
+"""Held-out evaluation: accuracy and mean loss of SimpleCNN over a ``DeviceMNIST`` split, and
+of ResNet-18 (top-1 and top-5) over a ``DeviceImages`` split.
 
 On the GPU the whole forward of an evaluation batch is ONE launch of the fused inference
 kernel (csrc/kernels/infer.hip: conv1 recomputed from the uint8 images, MFMA conv2, bias +
@@ -7,6 +8,16 @@ whether it is correct - no activation is stored), followed by the one-block tota
 that adds the batch into a running (int64 correct, fp64 loss) pair on the device; a split
 costs one device-to-host read.  On the CPU, and on the module path, the model's own forward
 runs under ``torch.no_grad()`` with the same tie rule and the same result type.
+
+ResNet-18 (:class:`ResNetEvaluator`, :func:`evaluate_resnet`): on the GPU the inference forward
+``ResNet.forward_infer`` - every conv + frozen BatchNorm (+ residual) (+ ReLU) one launch with
+the affine in the convolution's epilogue (csrc/kernels/conv_infer.h), the BatchNorm vectors
+folded once per call - then the one-wave-per-row tail kernel (prediction, loss, top-1 and
+top-5 hit per image) and the one-block totals kernel; again one device-to-host read per
+split.  ``engine="module"`` and the CPU run the model's own forward in ``eval()`` under
+``no_grad`` with the same tie and top-5 rules (the oracle path).  Evaluation only reads the
+model: no autograd graph, no gradient, no BatchNorm buffer and none of the training step's
+buffers is written, and ``model.training`` is restored.
 
 Sharding: :func:`eval_shard` partitions the split WITHOUT padding (``DistributedSampler`` pads
 with duplicates, which would bias the counts), so after :func:`all_reduce_result` the
@@ -33,10 +44,18 @@ class EvalResult:
     loss: torch.Tensor | None = None     # float32 [count]
     logits: torch.Tensor | None = None   # float32 [count, 10] (only when asked for)
     correct_rows: torch.Tensor | None = None  # int32 [count]: 1 where pred == label
+    correct5: int | None = None               # top-5 hits (ResNet evaluation only)
+    correct5_rows: torch.Tensor | None = None  # int32 [count]: 1 where the label is in the top 5
 
     @property
     def accuracy(self) -> float:
         return self.correct / self.count if self.count else float("nan")
+
+    @property
+    def top5(self) -> float:
+        if self.correct5 is None:
+            return float("nan")
+        return self.correct5 / self.count if self.count else float("nan")
 
     @property
     def mean_loss(self) -> float:
@@ -73,12 +92,14 @@ def all_reduce_result(res: EvalResult) -> EvalResult:
     if not dist.is_initialized() or dist.get_world_size() == 1:
         return res
     dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else torch.device("cpu")
-    cc = torch.tensor([res.correct, res.count], dtype=torch.int64, device=dev)
+    counts = [res.correct, res.count] + ([res.correct5] if res.correct5 is not None else [])
+    cc = torch.tensor(counts, dtype=torch.int64, device=dev)
     ls = torch.tensor([res.loss_sum], dtype=torch.float64, device=dev)
     dist.all_reduce(cc)
     dist.all_reduce(ls)
     cc = cc.cpu()
-    return dataclasses.replace(res, correct=int(cc[0]), count=int(cc[1]), loss_sum=float(ls.cpu()[0]))
+    out = dataclasses.replace(res, correct=int(cc[0]), count=int(cc[1]), loss_sum=float(ls.cpu()[0]))
+    return dataclasses.replace(out, correct5=int(cc[2])) if res.correct5 is not None else out
 
 
 def _check_indices(indices, n: int, device) -> torch.Tensor | None:
@@ -213,3 +234,136 @@ def evaluate(model, data: DeviceMNIST, device=None, dtype: str = "bf16", batch_s
     ev = FusedEvaluator(device, dtype, pxt)
     with torch.cuda.device(device):
         return ev.run(data, model_operands(model, dtype), batch_size, indices, want_logits)
+
+
+# ---------------------------------------------------------------------------- ResNet-18
+def top5_hit(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    """int32 [B]: 1 iff fewer than 5 classes ``j`` rank before the label - ``row[j] > row[label]``,
+    or ``row[j] == row[label]`` with ``j < label`` (the tail kernel's rule; with at most 5
+    classes every finite row is a hit)."""
+    xl = logits.gather(1, labels.view(-1, 1))
+    cls = torch.arange(logits.shape[1], device=logits.device).expand_as(logits)
+    before = (logits > xl) | ((logits == xl) & (cls < labels.view(-1, 1)))
+    return (before.sum(dim=1) < 5).to(torch.int32)
+
+
+def _check_activation_sizes(model, batch: int, size_hw):
+    """The kernels index pixels (and the reduction's elements) with ``int``: refuse a batch
+    any of whose activations would reach 2^31 elements (the stem's output is the largest)."""
+    h, w = int(size_hw[0]), int(size_hw[1])
+    oh, ow = (h + 2 * 3 - 7) // 2 + 1, (w + 2 * 3 - 7) // 2 + 1
+    biggest = max(batch * h * w * 4, batch * oh * ow * model.conv1.out_channels)
+    if biggest >= 2 ** 31:
+        raise ValueError(f"evaluate_resnet: a batch of {batch} {h}x{w} images has an activation of {biggest} "
+                         f">= 2^31 elements; lower the evaluation batch size")
+
+
+class ResNetEvaluator:
+    """The ResNet inference path's running totals (int64 [top-1, top-5], fp64 loss) and its
+    launch loop.  Nothing of the training step is shared: outputs and totals belong to the
+    evaluator, the model is only read."""
+
+    def __init__(self, device):
+        from .. import native
+
+        self.C = native.require()
+        self.device = torch.device(device)
+        self.tot = self.tot_loss = None
+
+    def run(self, model, data, batch_size: int = 256, indices=None, want_logits: bool = False) -> EvalResult:
+        """Evaluate rows ``indices`` (default: all) of the ``DeviceImages`` split on the CURRENT
+        stream."""
+        if data.device != self.device:
+            raise ValueError(f"evaluate: the split lives on {data.device}, the evaluator on {self.device}")
+        B = int(batch_size)
+        if B < 1:
+            raise ValueError("evaluate_resnet: batch_size must be >= 1")
+        idx = _check_indices(indices, len(data), self.device)
+        if idx is None:
+            idx = torch.arange(len(data), device=self.device)
+        idx = idx.to(torch.int64).contiguous()
+        n = idx.numel()
+        _check_activation_sizes(model, min(B, max(n, 1)), data.images_u8.shape[1:3])
+        dev = self.device
+        ncls = model.fc.weight.shape[0]
+        pred = torch.empty(n, dtype=torch.int32, device=dev)
+        correct = torch.empty(n, dtype=torch.int32, device=dev)
+        correct5 = torch.empty(n, dtype=torch.int32, device=dev)
+        loss = torch.empty(n, dtype=torch.float32, device=dev)
+        logits = torch.empty(n, ncls, dtype=torch.float32, device=dev) if want_logits else None
+        if n == 0:
+            return EvalResult(0, 0, 0.0, pred, loss, logits, correct, 0, correct5)
+        if self.tot is None:
+            self.tot = torch.zeros(2, dtype=torch.int64, device=dev)
+            self.tot_loss = torch.zeros(1, dtype=torch.float64, device=dev)
+        self.tot.zero_()
+        self.tot_loss.zero_()
+        was_training = model.training
+        try:
+            with torch.no_grad():
+                folded = model.fold_bn()  # once per evaluation call
+                for s in range(0, n, B):  # (the last batch may be ragged)
+                    b = min(B, n - s)
+                    x, y = data.gather(idx[s:s + b])
+                    lg = model.forward_infer(x, folded)
+                    self.C.resnet_eval_tail(lg, y, pred[s:], loss[s:], correct[s:], correct5[s:])
+                    self.C.resnet_eval_totals(correct[s:], correct5[s:], loss[s:], b, self.tot, self.tot_loss)
+                    if logits is not None:
+                        logits[s:s + b] = lg
+        finally:
+            model.train(was_training)
+        tot, ls = self.tot.cpu(), float(self.tot_loss.cpu()[0])  # (the split's only waits)
+        return EvalResult(int(tot[0]), n, ls, pred, loss, logits, correct, int(tot[1]), correct5)
+
+
+def evaluate_resnet_forward(model, data, batch_size: int = 256, indices=None,
+                            want_logits: bool = False) -> EvalResult:
+    """The model's own forward in ``eval()`` under ``no_grad`` (CPU, and the GPU module path),
+    per batch, with the tail kernel's tie and top-5 rules in torch."""
+    dev = data.device
+    idx = _check_indices(indices, len(data), dev)
+    if idx is None:
+        idx = torch.arange(len(data), device=dev)
+    idx = idx.to(torch.int64)
+    n = idx.numel()
+    B = int(batch_size)
+    if B < 1:
+        raise ValueError("evaluate_resnet: batch_size must be >= 1")
+    _check_activation_sizes(model, min(B, max(n, 1)), data.images_u8.shape[1:3])
+    preds, losses, lgs, hits5 = [], [], [], []
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for s in range(0, n, B):
+                x, y = data.gather(idx[s:s + B])
+                lg = model(x).float()
+                preds.append(lowest_argmax(lg).to(torch.int32))
+                losses.append(torch.logsumexp(lg, dim=1) - lg.gather(1, y.view(-1, 1))[:, 0])
+                hits5.append(top5_hit(lg, y))
+                if want_logits:
+                    lgs.append(lg)
+    finally:
+        model.train(was_training)
+    pred = torch.cat(preds) if preds else torch.empty(0, dtype=torch.int32, device=dev)
+    loss = torch.cat(losses) if losses else torch.empty(0, dtype=torch.float32, device=dev)
+    rows5 = torch.cat(hits5) if hits5 else torch.empty(0, dtype=torch.int32, device=dev)
+    labels = data.labels.index_select(0, idx)
+    rows = (pred == labels).to(torch.int32)
+    loss_sum = float(loss.double().cpu().cumsum(0)[-1]) if n else 0.0  # fp64, index order
+    return EvalResult(int(rows.sum()), n, loss_sum, pred, loss, torch.cat(lgs) if lgs else None, rows,
+                      int(rows5.sum()), rows5)
+
+
+def evaluate_resnet(model, data, device=None, batch_size: int = 256, indices=None, engine: str = "fused",
+                    want_logits: bool = False) -> EvalResult:
+    """Evaluate a ResNet on rows ``indices`` of a ``DeviceImages`` split: on a GPU with
+    ``engine="fused"`` the fused conv + BatchNorm inference path; on the CPU and with
+    ``engine="module"`` the model's own forward in ``eval()``."""
+    device = torch.device(device) if device is not None else data.device
+    if engine not in ("fused", "module"):
+        raise ValueError(f"evaluate_resnet: engine must be fused or module, got {engine!r}")
+    if device.type != "cuda" or engine == "module":
+        return evaluate_resnet_forward(model, data, batch_size, indices, want_logits)
+    with torch.cuda.device(device):
+        return ResNetEvaluator(device).run(model, data, batch_size, indices, want_logits)

@@ -20,6 +20,7 @@ PyTorch oracle), with the same launcher, logging, checkpoint and resume contract
 """
 from __future__ import annotations
 
+import contextlib
 import dataclasses
 import os
 import time
@@ -28,7 +29,7 @@ import torch
 import torch.distributed as dist
 
 from ..data import (DeviceImageLoader, DeviceImages, DeviceMNIST, DeviceMNISTLoader, get_dataloader,
-                    load_mnist, synthetic_imagenet)
+                    load_mnist, synthetic_imagenet, synthetic_imagenet_test)
 from ..models import SimpleCNN, resnet18
 from ..models.layers import buffer_space, flat_space
 from ..ops import CrossEntropyLoss, FusedSGD
@@ -77,6 +78,7 @@ class TrainOptions:
     eval_every: int = 0               # evaluate the held-out split after every Nth epoch (0: never)
     eval_batch_size: int = 1000       # images per evaluation launch / forward
     eval_only: bool = False           # resume from the newest checkpoint, evaluate, exit
+    eval_size: int = 0                # resnet18: images of the synthetic held-out split (0: none)
 
 
 def validate_options(opts: TrainOptions):
@@ -84,9 +86,14 @@ def validate_options(opts: TrainOptions):
     by every rank)."""
     if opts.eval_every < 0 or opts.eval_batch_size < 1:
         raise ValueError("--eval_every must be >= 0 and --eval_batch_size >= 1")
-    if opts.model == "resnet18" and (opts.eval_every or opts.eval_only):
+    if opts.eval_size < 0:
+        raise ValueError("--eval_size must be >= 0")
+    if opts.model == "resnet18" and (opts.eval_every or opts.eval_only) and not opts.eval_size:
         raise ValueError("--eval_every / --eval_only evaluate SimpleCNN on the MNIST test split; the synthetic "
-                         "ImageNet set of --model resnet18 has no held-out split")
+                         "ImageNet set of --model resnet18 has no held-out split unless --eval_size N builds one")
+    if opts.model != "resnet18" and opts.eval_size:
+        raise ValueError("--eval_size sizes the synthetic held-out split of --model resnet18; simplecnn's "
+                         "split is the MNIST test set")
 
 
 def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
@@ -147,7 +154,13 @@ def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
         loader, sampler = get_dataloader(batch_size, world_size, rank, root=opts.data_root,
                                          source=opts.data, num_workers=opts.num_workers)
     edata = None
-    if opts.eval_every or opts.eval_only:
+    if (opts.eval_every or opts.eval_only) and opts.model == "resnet18":
+        timgs, tlabels = synthetic_imagenet_test(opts.eval_size, opts.image_size, opts.num_classes,
+                                                 n_train=opts.dataset_size)
+        edata, tsrc = DeviceImages(timgs, tlabels, device), "synthetic"
+        if rank == 0:
+            print(f"Rank {rank}: Eval split: {tsrc} ({len(edata)} images)", flush=True)
+    elif opts.eval_every or opts.eval_only:
         timgs, tlabels, tsrc = load_mnist(opts.data_root, opts.data, split="test")
         edata = DeviceMNIST(timgs, tlabels, device, tsrc)
         if rank == 0:
@@ -247,10 +260,13 @@ def run_eval(model, engine, edata, device, opts, rank: int, world_size: int, fus
     rank), then the totals over all ranks.  Fused GPU path: the inference kernel (on the
     engine's stream with the engine's operands, or built from the bare model's parameters);
     module path and CPU: the model's forward under ``no_grad``.  Collective."""
-    from .evaluation import all_reduce_result, eval_shard, evaluate
+    from .evaluation import all_reduce_result, eval_shard, evaluate, evaluate_resnet
 
     idx = eval_shard(len(edata), world_size, rank)
-    if engine is not None:
+    if opts.model == "resnet18":  # GPU: the fused conv + BatchNorm inference path; CPU: the module forward
+        with _rank0_buffers(model, world_size):
+            res = evaluate_resnet(model, edata, device, opts.eval_batch_size, idx, engine="fused")
+    elif engine is not None:
         res = engine.evaluate(edata, opts.eval_batch_size, idx)
     else:
         res = evaluate(model, edata, device, opts.dtype, opts.eval_batch_size, idx,
@@ -258,10 +274,40 @@ def run_eval(model, engine, edata, device, opts, rank: int, world_size: int, fus
     return all_reduce_result(res)
 
 
+@contextlib.contextmanager
+def _rank0_buffers(model, world_size: int):
+    """Evaluate with rank 0's BatchNorm running statistics on every rank - the ones DDP
+    broadcasts before each forward and the ones the checkpoint holds (a rank's own drift from
+    them after its last step) - so the totals do not depend on the sharding.  This rank's own
+    buffers are put back afterwards, bit for bit: evaluation leaves no trace.  Collective."""
+    bs = buffer_space(model) if world_size > 1 else None
+    if bs is None:
+        yield
+        return
+    flats = bs.flat_list()
+    saved = [t.clone() for t in flats]
+    staged = dist.get_backend() != "nccl"  # gloo control plane: collectives on CPU tensors
+    with torch.no_grad():
+        for t in flats:
+            if staged and t.is_cuda:
+                c = t.cpu()
+                dist.broadcast(c, src=0)
+                t.copy_(c)
+            else:
+                dist.broadcast(t, src=0)
+    try:
+        yield
+    finally:
+        with torch.no_grad():
+            for t, s in zip(flats, saved):
+                t.copy_(s)
+
+
 def _log_eval(rank: int, epoch: int, res):
     if rank == 0:
+        top5 = "" if res.correct5 is None else f" | Top-5: {100.0 * res.top5:.2f}% ({res.correct5}/{res.count})"
         print(f"Epoch {epoch} | Eval | Loss: {res.mean_loss:.4f} | Accuracy: {100.0 * res.accuracy:.2f}% "
-              f"({res.correct}/{res.count})", flush=True)
+              f"({res.correct}/{res.count}){top5}", flush=True)
 
 
 def module_comm(comm: str) -> str:
@@ -484,5 +530,7 @@ def _record_metrics(opts, rank, ws, epoch, nsteps, batch, dt, samples, ev=None):
            "images_per_sec_aggregate": samples * ws / dt if dt > 0 else None}
     if ev is not None:
         rec["eval_loss"], rec["eval_accuracy"] = ev.mean_loss, ev.accuracy
+        if ev.correct5 is not None:
+            rec["eval_top5"] = ev.top5
     with open(opts.metrics_json, "a") as f:
         f.write(json.dumps(rec) + "\n")

@@ -75,6 +75,19 @@ class BasicBlock(nn.Module):
             return conv_bn_act(out, self.conv2, self.bn2, res=idt, relu=True)
         return conv_bn_act(out, self.conv2, self.bn2, res=x, relu=True, stash=stash)
 
+    def forward_infer(self, x, folded):
+        """Evaluation forward (NHWC bf16, frozen statistics): every conv + BatchNorm (+ residual)
+        (+ ReLU) is one fused inference launch; ``folded`` = :meth:`ResNet.fold_bn`'s operands."""
+        from ..ops.resnet_fn import conv_bn_act_infer
+
+        w = folded.get
+        out = conv_bn_act_infer(x, self.conv1, folded[self.bn1], relu=True, weight=w(self.conv1))
+        idt = x
+        if self.downsample is not None:
+            idt = conv_bn_act_infer(x, self.downsample[0], folded[self.downsample[1]], relu=False,
+                                    weight=w(self.downsample[0]))
+        return conv_bn_act_infer(out, self.conv2, folded[self.bn2], res=idt, relu=True, weight=w(self.conv2))
+
 
 class ResNet(nn.Module):
     def __init__(self, layers=(2, 2, 2, 2), num_classes=1000):
@@ -122,6 +135,34 @@ class ResNet(nn.Module):
         for b in self.blocks():
             h = b.forward_hip(h)
         return R.linear_head(R.global_avgpool(h), self.fc.weight, self.fc.bias)
+
+    def fold_bn(self) -> dict:
+        """The inference operands, made once per evaluation call: {BatchNorm module: folded
+        (sc, sh)} and {conv module: its bf16 MFMA weight} for :meth:`forward_infer`."""
+        from ..ops.resnet_fn import bn_fold, conv_weight_infer
+
+        ops = {m: bn_fold(m) for m in self.modules() if isinstance(m, nn.BatchNorm2d)}
+        with torch.no_grad():
+            ops.update({m: conv_weight_infer(m) for m in self.modules() if isinstance(m, Conv2d)})
+        return ops
+
+    def forward_infer(self, x: torch.Tensor, folded: dict | None = None) -> torch.Tensor:
+        """Inference forward on the GPU with the BatchNorm running statistics folded into the
+        convolutions' epilogues (no autograd graph; parameters and buffers are only read).
+        x: NHWC4 bf16 [B,H,W,4] (NCHW float is converted); returns fp32 logits.  ``forward`` /
+        ``forward_hip`` are untouched: ``model.eval(); model(x)`` keeps the training kernels."""
+        from ..ops import resnet_fn as R
+
+        if x.dtype != torch.bfloat16:  # NCHW float images
+            x = R.to_nhwc4(x)
+        if folded is None:
+            folded = self.fold_bn()
+        with torch.no_grad():
+            h = R.conv_bn_act_infer(x, self.conv1, folded[self.bn1], relu=True, weight=folded.get(self.conv1))
+            h = R.maxpool3x3s2_infer(h)
+            for b in self.blocks():
+                h = b.forward_infer(h, folded)
+            return R.head_infer(h, self.fc.weight, self.fc.bias)
 
 
 def resnet18(num_classes: int = 1000) -> ResNet:

@@ -351,3 +351,76 @@ def global_avgpool(x):
 
 def linear_head(x, w, b):
     return _LinearHead.apply(x, w, b)
+
+
+# ---------------------------------------------------------------- inference (evaluation)
+def bn_fold(bn):
+    """The frozen BatchNorm as a per-channel affine ``(sc, sh)``: ``invstd = rsqrt(running_var +
+    eps)``, ``sc = invstd * gamma``, ``sh = fma(-running_mean, sc, beta)`` (bn_affine.h's
+    definition), fp32 on the parameters' device.  Fold once per evaluation call."""
+    C = bn.num_features
+    dev = bn.running_mean.device
+    f = lambda t: t.detach().float().contiguous()  # noqa: E731
+    gamma = f(bn.weight) if bn.weight is not None else torch.ones(C, device=dev)
+    beta = f(bn.bias) if bn.bias is not None else torch.zeros(C, device=dev)
+    sc, sh = torch.empty(C, device=dev), torch.empty(C, device=dev)
+    _C().bn_fold(f(bn.running_mean), f(bn.running_var), gamma, beta, float(bn.eps), sc, sh)
+    return sc, sh
+
+
+def conv_weight_infer(conv):
+    """The convolution's bf16 MFMA operand (OHWI; the stem's 3 channels zero-padded to 4): the
+    flat bf16 copy FusedSGD keeps when the model is flattened, else a conversion - made once
+    per evaluation call, not per batch."""
+    w = conv.weight
+    wk = _weight_bf16(w)
+    if w.shape[-1] == 3:  # stem
+        fs = getattr(w, "_ddp_amd_fs", None)
+        wp = fs.bf16_pad4_view(w) if fs is not None else None
+        wk = wp if wp is not None else torch.nn.functional.pad(wk, (0, 1))
+    return wk
+
+
+def conv_bn_act_infer(x, conv, bn_folded, res=None, relu=True, weight=None):
+    """conv -> frozen BatchNorm -> (+ res) -> (ReLU) in ONE launch (split-K plans: two): the
+    affine, the residual and the ReLU ride in the convolution's epilogue on the fp32
+    accumulators, rounded to bf16 once; no raw conv output, no statistics, no bn_apply.
+    A plain function: no autograd graph, nothing saved.  ``x``: NHWC bf16 (stem: NHWC4);
+    ``bn_folded``: :func:`bn_fold`'s ``(sc, sh)``; ``weight``: :func:`conv_weight_infer`'s
+    operand when the caller prepared it (else it is made here)."""
+    sc, sh = bn_folded
+    N, H, W_, Cin = x.shape
+    Cout, KH, KW, _ = conv.weight.shape
+    stride, pad = conv.stride, conv.padding
+    OH, OW = (H + 2 * pad - KH) // stride + 1, (W_ + 2 * pad - KW) // stride + 1
+    wk = weight if weight is not None else conv_weight_infer(conv)
+    y = torch.empty(N, OH, OW, Cout, dtype=BF16, device=x.device)
+    C = _C()
+    _, _, splits, _, _, _ = C.conv_gemm_plan(x, y, KH, KW, stride, pad)
+    part = torch.empty(splits * y.numel(), device=x.device) if splits > 1 else None
+    C.conv_gemm_infer(x, wk, sc, sh, res.contiguous() if res is not None else None, y, KH, KW, stride, pad,
+                      bool(relu), part)
+    return y
+
+
+def maxpool3x3s2_infer(x):
+    """The 3x3 / s2 max pool of a materialised activation (no BatchNorm affine, no autograd)."""
+    N, H, W, Cc = x.shape
+    OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    y = torch.empty(N, OH, OW, Cc, dtype=BF16, device=x.device)
+    am = torch.empty(N, OH, OW, Cc, dtype=torch.uint8, device=x.device)
+    _C().maxpool_fwd(x.contiguous(), y, am, None)
+    return y
+
+
+def head_infer(x, w, b):
+    """Global average pool + fp32 classifier head: ``avgpool_fwd`` and ``sgemm`` -> logits."""
+    N, H, W, Cc = x.shape
+    C = _C()
+    pooled = torch.empty(N, Cc, device=x.device)
+    C.avgpool_fwd(x.contiguous(), pooled)
+    K, NO = Cc, w.shape[0]
+    out = torch.empty(N, NO, device=x.device)
+    C.sgemm(N, NO, K, pooled, K, 1, w.detach().float().contiguous(), 1, K, out,
+            b.detach().float().contiguous() if b is not None else None, 1.0)
+    return out

@@ -85,10 +85,13 @@ def parse_args(argv=None):
                    help="after every epoch check that all ranks' parameters and momentum are bitwise equal")
     p.add_argument("--eval_every", type=int, default=0,
                    help="evaluate the held-out test split (sharded over the ranks, exact counts) after every "
-                        "Nth epoch; 0 = never (simplecnn)")
+                        "Nth epoch; 0 = never (simplecnn; resnet18 with --eval_size)")
     p.add_argument("--eval_batch_size", type=int, default=1000, help="images per evaluation batch")
     p.add_argument("--eval_only", action="store_true",
                    help="resume from the newest checkpoint, evaluate the test split, exit")
+    p.add_argument("--eval_size", type=int, default=0,
+                   help="resnet18: build a synthetic held-out split of N images (at --image_size / --num_classes) "
+                        "for --eval_every / --eval_only; 0 = none")
     return p.parse_args(argv)
 
 
@@ -106,7 +109,7 @@ def main(argv=None):
                         num_classes=a.num_classes, dataset_size=a.dataset_size,
                         graph_module=a.graph_module, verify_replicas=a.verify_replicas,
                         force_allreduce=a.force_allreduce, eval_every=a.eval_every,
-                        eval_batch_size=a.eval_batch_size, eval_only=a.eval_only,
+                        eval_batch_size=a.eval_batch_size, eval_only=a.eval_only, eval_size=a.eval_size,
                         stall=tuple(float(v) for v in a.stall_at.split(":")) if a.stall_at else None,
                         fault=tuple(int(v) for v in a.fault_at.split(":")) if a.fault_at else None)
     validate_options(opts)
