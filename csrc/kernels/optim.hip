@@ -97,23 +97,39 @@ void noop(int blocks, int* sink, hipStream_t s) {
 }
 
 // Few-row slabs (the ResNet weight gradients split over 1-16 pixel chunks): one thread
-// per 4 consecutive outputs summing rows 0..R-1 in order - the 64-output x 4-row-group
-// blocks of grad_reduce_kernel would leave most lanes idle and launch 10^4 tiny blocks.
+// per 4 consecutive outputs - the 64-output x 4-row-group blocks of grad_reduce_kernel
+// would leave most lanes idle and launch 10^4 tiny blocks.  The float operations are those
+// of slab_reduce.h at GR = 4 (rows <= 16): group g sums rows g, g + 4, ... from +0.0f, the
+// four group sums are added in order, then the same epilogue - the same bits as
+// grad_reduce_kernel<4>, so a result does not depend on which kernel the buffers' alignment
+// selects.
 __global__ __launch_bounds__(256) void slab_reduce_rows_kernel(SlabSeg sg) {
   const long n4 = sg.n >> 2;
   const long stride = (long)gridDim.x * blockDim.x;
   for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < n4; q += stride) {
     const float* src = sg.slab + sg.src_off + 4 * q;
-    float4 a = *reinterpret_cast<const float4*>(src);
-    for (int r = 1; r < sg.rows; ++r) {
-      const float4 b = *reinterpret_cast<const float4*>(src + (long)r * sg.row_stride);
-      a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
+    float4 g[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) g[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int r0 = 0; r0 < sg.rows; r0 += 4) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (r0 + u < sg.rows) {
+          const float4 b = *reinterpret_cast<const float4*>(src + (long)(r0 + u) * sg.row_stride);
+          g[u].x += b.x; g[u].y += b.y; g[u].z += b.z; g[u].w += b.w;
+        }
+      }
     }
-    a.x *= sg.scale; a.y *= sg.scale; a.z *= sg.scale; a.w *= sg.scale;
+    float4 a = g[0];
+#pragma unroll
+    for (int u = 1; u < 4; ++u) { a.x += g[u].x; a.y += g[u].y; a.z += g[u].z; a.w += g[u].w; }
     float4* d = reinterpret_cast<float4*>(sg.dst + 4 * q);
-    if (sg.accum) {
+    if (sg.accum) {  // one fma, as slab_reduce_chunk
       const float4 o = *d;
-      a.x += o.x; a.y += o.y; a.z += o.z; a.w += o.w;
+      a.x = fmaf(a.x, sg.scale, o.x); a.y = fmaf(a.y, sg.scale, o.y);
+      a.z = fmaf(a.z, sg.scale, o.z); a.w = fmaf(a.w, sg.scale, o.w);
+    } else {
+      a.x *= sg.scale; a.y *= sg.scale; a.z *= sg.scale; a.w *= sg.scale;
     }
     *d = a;
   }

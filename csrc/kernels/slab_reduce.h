@@ -102,8 +102,9 @@ __device__ __forceinline__ void slab_reduce_chunk(const SlabSet& ss, long q, flo
     float g = part[c];
 #pragma unroll
     for (int qq = 1; qq < GR; ++qq) g += part[qq * 64 + c];
-    g *= sg.scale;
-    if (sg.accum) g += sg.dst[i];
+    // explicit: one fma with `accum`, one product without (left to the compiler's contraction
+    // choice the bits could differ between the kernels that share this order)
+    g = sg.accum ? fmaf(g, sg.scale, sg.dst[i]) : g * sg.scale;
     if (ss.sys_store) st_sys(sg.dst + i, g);
     else sg.dst[i] = g;
     if (ss.sgd.update && sg.p) {  // single-process step: the gradient is final -> fused SGD
@@ -249,8 +250,7 @@ __device__ __forceinline__ void slab_fused_finish(const SlabSet& ss, const SlabF
     float gsum = part[(j * 16) * 64 + c];
 #pragma unroll
     for (int qq = 1; qq < 16; ++qq) gsum += part[(j * 16 + qq) * 64 + c];
-    gsum *= pl.scale;
-    if (pl.accum) gsum += pl.dst[i];
+    gsum = pl.accum ? fmaf(gsum, pl.scale, pl.dst[i]) : gsum * pl.scale;  // as slab_reduce_chunk
     if (ss.sys_store) st_sys(pl.dst + i, gsum);
     else pl.dst[i] = gsum;
     if (ss.sgd.update && pl.p) {

@@ -1,0 +1,199 @@
+"""A-priori rounding bounds, the error / bound ratio and the CPU replays shared by
+tests/test_simplecnn_kernels_elementwise_gpu.py (the HIP kernels) and
+tests/test_simplecnn_kernel_bounds_cpu.py (a float32 emulation of a correct kernel, and of
+subtly wrong ones).  Nothing here is calibrated on a kernel's output.
+
+u = 2**-24 is the fp32 unit roundoff, n the number of accumulated terms, A the same operation
+on absolute values:
+
+    fp32 outputs and slabs      E = 2 n u A          (bf16 operands: exact products)
+                                E = 3 n u A          (exact-fp32 builds: the products round too)
+    bf16 outputs                2**-8 (|ref| + E) + E
+
+The bf16 store rounds the value the kernel computed, which is within E of the reference, hence
+|ref| + E under the 2**-8.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+U = 2.0 ** -24
+BF_EPS = 2.0 ** -8
+
+
+def acc_bound(n, A, f32_operands=False):
+    """fp32 accumulation of n terms whose absolute values sum to A."""
+    return (3.0 if f32_operands else 2.0) * n * U * A
+
+
+def bf16_store_bound(ref, E):
+    return BF_EPS * (ref.abs() + E) + E
+
+
+def ratio(family, shape, out, ref, bound, what, tag="KERN_RATIO"):
+    """Prints and returns max |out - ref| / bound; asserts every element written and in bound."""
+    o = out.detach().cpu().double()
+    assert o.shape == ref.shape, (what, o.shape, ref.shape)
+    assert bool(torch.isfinite(o).all()), f"{what}: unwritten / non-finite elements"
+    rr = (o - ref).abs() / (bound + 1e-300)
+    r = rr.max().item() if rr.numel() else 0.0
+    print(f"{tag} {family} {shape} {r:.3e}")
+    if r > 1.0:
+        i = tuple(int(v) for v in torch.nonzero(rr == rr.max())[0])
+        what += f" at {i}: out {o[i].item()!r} ref {ref[i].item()!r}; {int((rr > 1).sum())} elements out of bound"
+    assert r <= 1.0, f"{what}: error / bound = {r:.3f}"
+    return r
+
+
+def ratio_value(out, ref, bound):
+    """max |out - ref| / bound without asserting (the CPU file's mutation checks)."""
+    return ((out.detach().cpu().double() - ref).abs() / (bound + 1e-300)).max().item()
+
+
+# ------------------------------------------------------------------------------- SGD
+def sgd_bounds(p, g, m, lr, momentum, dampening, wd, nesterov, first_step):
+    """(bound on the new parameter, bound on the new momentum buffer) of common.h sgd_one.
+
+    sgd_one: d = fma(wd, p, +-g) [1 rounding]; buf = d on the first step, else
+    fma(fl(1 - dampening), d, fl(momentum * m)) [3: the product, the difference, the fma];
+    d = fma(momentum, buf, d) with nesterov [1]; p' = fma(-lr, d, p) [1].  Each rounding is at
+    most u times a partial result that the same formula on absolute values (D1, BUF, D2, P
+    below) dominates, and every later step scales it by a factor that formula contains too:
+    at most 4 roundings reach the buffer and 6 the parameter.
+
+        |buf' - ref| <= 4 u BUF          |p' - ref| <= 6 u P
+    """
+    p, g = p.abs(), g.abs()
+    D1 = g + abs(wd) * p
+    if momentum != 0.0:
+        BUF = D1 if first_step else abs(1.0 - dampening) * D1 + abs(momentum) * m.abs()
+        D2 = abs(momentum) * BUF + D1 if nesterov else BUF
+    else:
+        BUF = torch.zeros_like(D1)
+        D2 = D1
+    P = p + abs(lr) * D2
+    return 6 * U * P, 4 * U * BUF
+
+
+# ----------------------------------------------------------------------- shadow layouts
+SHADOW_BF16, SHADOW_BF16_TAPT, SHADOW_BF16_FCFRAG, SHADOW_BF16_PAD4, SHADOW_F32_TAPT, SHADOW_F32_FCFRAG = range(1, 7)
+
+
+def shadow_index(kind, n, a=0, b=0, c=0):
+    """Destination index of every region element j = 0..n-1 (int64 array) - launchers.h:
+    plain copy; TAPT: OHWI [co][tap][ci] -> [tap][ci][co] (a = Co, b = taps, c = Ci); FCFRAG:
+    [o][hw][c] -> [o][hw/16][c/16][(c/4)%4][hw%16][c%4] (a = HW, b = C); PAD4: [..][3] ->
+    [..][4]."""
+    j = np.arange(n, dtype=np.int64)
+    if kind == SHADOW_BF16:
+        return j
+    if kind in (SHADOW_BF16_TAPT, SHADOW_F32_TAPT):
+        per = b * c
+        co = j // per
+        return (j - co * per) * a + co
+    if kind in (SHADOW_BF16_FCFRAG, SHADOW_F32_FCFRAG):
+        HW, C = a, b
+        o, rem = j // (HW * C), j % (HW * C)
+        hw, ch = rem // C, rem % C
+        G, T = HW // 16, C // 16
+        return ((((o * G + hw // 16) * T + ch // 16) * 4 + (ch // 4) % 4) * 16 + hw % 16) * 4 + ch % 4
+    if kind == SHADOW_BF16_PAD4:
+        return (j // 3) * 4 + j % 3
+    raise ValueError(kind)
+
+
+def shadow_dst_numel(kind, n):
+    return n // 3 * 4 if kind == SHADOW_BF16_PAD4 else n
+
+
+def shadow_is_f32(kind):
+    return kind in (SHADOW_F32_TAPT, SHADOW_F32_FCFRAG)
+
+
+# ------------------------------------------------------------- fixed-order slab reduction
+def reduce_groups(rows_of_segments):
+    """grad_reduce_groups (optim.hip): 16 when the deepest segment has >= 64 rows, else 4."""
+    return 16 if max(rows_of_segments) >= 64 else 4
+
+
+def replay_reduce(rows32, GR):
+    """slab_reduce.h's order in float32: group g adds rows g, g + GR, ... sequentially from
+    +0.0, the group sums are then added in order 0..GR-1.  rows32: float32 array [rows][n]."""
+    rows32 = np.asarray(rows32, dtype=np.float32)
+    R, n = rows32.shape
+    part = []
+    for g in range(GR):
+        acc = np.zeros(n, dtype=np.float32)
+        for r in range(g, R, GR):
+            acc = (acc + rows32[r]).astype(np.float32)
+        part.append(acc)
+    tot = part[0]
+    for g in range(1, GR):
+        tot = (tot + part[g]).astype(np.float32)
+    return tot
+
+
+def replay_sequential(rows32):
+    rows32 = np.asarray(rows32, dtype=np.float32)
+    acc = np.zeros(rows32.shape[1], dtype=np.float32)
+    for r in range(rows32.shape[0]):
+        acc = (acc + rows32[r]).astype(np.float32)
+    return acc
+
+
+def replay_pairwise(rows32):
+    v = [np.asarray(r, dtype=np.float32) for r in rows32]
+    while len(v) > 1:
+        v = [(v[i] + v[i + 1]).astype(np.float32) if i + 1 < len(v) else v[i] for i in range(0, len(v), 2)]
+    return v[0]
+
+
+def replay_finish(tot32, scale, prior32=None):
+    """The reducer's epilogue on a group total (slab_reduce.h): the float32 product with the
+    scale, or with `accum` ONE fma(total, scale, prior).  The fma is evaluated in extended
+    precision (the product of two float32 is exact there) and rounded once to float32."""
+    s = np.float32(scale)
+    tot32 = np.asarray(tot32, dtype=np.float32)
+    if prior32 is None:
+        return (tot32 * s).astype(np.float32)
+    prior32 = np.asarray(prior32, dtype=np.float32)
+    return (tot32.astype(np.longdouble) * np.longdouble(s) + prior32.astype(np.longdouble)).astype(np.float32)
+
+
+def reduce_bound(rows64, scale, prior64=None):
+    """|out - scale * sum rows (+ prior)| <= 2 (rows + 2) u (|scale| sum |rows| + |prior|)."""
+    R = rows64.shape[0]
+    A = abs(scale) * rows64.abs().sum(0)
+    if prior64 is not None:
+        A = A + prior64.abs()
+    return 2 * (R + 2) * U * A
+
+
+# --------------------------------------------------------------------------- xent_rows
+def xent_rows_bounds(x, absum, G, labels, gscale, p, rows):
+    """(dlogits bound [B,NO], row-loss bound [B]) of xent_rows (common.h xent_batch_block,
+    xent_row_dl) for float64 logits x = bias + the sum of G - 1 partials, absum = |bias| + the
+    sum of their absolute values, p the float64 softmax and rows the float64 row losses.
+
+    The logit itself: G fp32 adds, e_l = 2 G u absum (per row: the worst class).  With D =
+    max |x - max| the ResNet cross-entropy bound (tests/test_resnet_ops_elementwise_gpu.py)
+    takes the argument error u D; here the argument also carries 2 e_l (x and the maximum):
+
+        |dl - ref| <= g (p (2 D + 64) u + 2 p e_l + 2 u)
+
+    The row loss is evaluated as (mx + log se) - x[label]: besides (D + 64) u max(1, |ref|) and
+    the two logits' own error 2 e_l, the sum mx + log se and the difference round at the
+    logits' magnitude: u (|mx| + log se) + u |ref| <= 2 u (|mx| + |x_label|) + 2 u log se, and
+    2 u log se <= 6 u (at most 16 classes) lies inside the constant 64:
+
+        |loss - ref| <= (D + 64) u max(1, |ref|) + 2 e_l + 2 u (|mx| + |x_label|)
+    """
+    B = x.shape[0]
+    e_l = (2 * G * U * absum).max(1).values
+    mx = x.max(1).values
+    D = (x - mx[:, None]).abs().max(1).values
+    bd = gscale * (p * (2 * D[:, None] + 64) * U + 2 * p * e_l[:, None] + 2 * U)
+    xl = x[torch.arange(B), labels.long()]
+    bl = (D + 64) * U * rows.abs().clamp(min=1.0) + 2 * e_l + 2 * U * (mx.abs() + xl.abs())
+    return bd, bl

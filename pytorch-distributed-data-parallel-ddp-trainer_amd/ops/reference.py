@@ -255,3 +255,128 @@ def gemm64(A, B, bias=None, alpha=1.0, prior=None):
     if prior is not None:
         out = out + _d(prior)
     return out
+
+
+# ---------------------------------------------------------------------------------------
+# float64 CPU references of the SimpleCNN step kernels (conv3x3.hip, conv1.hip, linear.hip,
+# optim.hip), written tap by tap from the definition - independent of torch's convolution
+# operators, against which tests/test_simplecnn_kernel_bounds_cpu.py holds them.  NHWC
+# activations, OHWI weights.
+def _shift(x, dh, dw):
+    """x [B,H,W,C] -> x at pixel (h + dh, w + dw), zero outside the image."""
+    B, H, W, C = x.shape
+    out = torch.zeros_like(x)
+    h0, h1, w0, w1 = max(0, -dh), min(H, H - dh), max(0, -dw), min(W, W - dw)
+    if h0 < h1 and w0 < w1:
+        out[:, h0:h1, w0:w1] = x[:, h0 + dh:h1 + dh, w0 + dw:w1 + dw]
+    return out
+
+
+def conv3x3_64(x, w_ohwi, bias=None, relu=False):
+    """y[n,h,w,co] = sum_{kh,kw,ci} x[n,h+kh-1,w+kw-1,ci] w[co,kh,kw,ci] (+ bias), float64."""
+    x, w, bias = _d(x), _d(w_ohwi), _d(bias)
+    y = torch.zeros(*x.shape[:3], w.shape[0], dtype=torch.float64)
+    for tap in range(9):
+        kh, kw = divmod(tap, 3)
+        y += torch.einsum("nhwi,oi->nhwo", _shift(x, kh - 1, kw - 1), w[:, kh, kw, :])
+    if bias is not None:
+        y = y + bias
+    return torch.relu(y) if relu else y
+
+
+def conv3x3_dgrad64(dy, w_ohwi):
+    """dx[n,h,w,ci] = sum_{kh,kw,co} dy[n,h+1-kh,w+1-kw,co] w[co,kh,kw,ci], float64."""
+    dy, w = _d(dy), _d(w_ohwi)
+    dx = torch.zeros(*dy.shape[:3], w.shape[3], dtype=torch.float64)
+    for tap in range(9):
+        kh, kw = divmod(tap, 3)
+        dx += torch.einsum("nhwo,oi->nhwi", _shift(dy, 1 - kh, 1 - kw), w[:, kh, kw, :])
+    return dx
+
+
+def conv3x3_wgrad64(dy, x, rows=None, image=None):
+    """(dW OHWI [Co,3,3,Ci], db [Co]) in float64, of output rows [rows[0], rows[1]) of one
+    image only when given (one split-K slab row of conv3x3_wgrad)."""
+    dy, x = _d(dy), _d(x)
+    if image is not None:
+        dy, x = dy[image:image + 1], x[image:image + 1]
+    if rows is not None:
+        keep = torch.zeros_like(dy)
+        keep[:, rows[0]:rows[1]] = 1.0
+        dy = dy * keep
+    dw = torch.zeros(dy.shape[3], 3, 3, x.shape[3], dtype=torch.float64)
+    for tap in range(9):
+        kh, kw = divmod(tap, 3)
+        dw[:, kh, kw, :] = torch.einsum("nhwo,nhwi->oi", dy, _shift(x, kh - 1, kw - 1))
+    return dw, dy.sum(dim=(0, 1, 2))
+
+
+def conv1_64(x, w_o9, bias, relu=True):
+    """conv1: x [B,H,W] (float, or uint8 read as x / 255) -> relu(conv3x3 + bias) [B,H,W,Co]."""
+    xd = _d(x) / 255.0 if x.dtype == torch.uint8 else _d(x)
+    return conv3x3_64(xd.unsqueeze(-1), _d(w_o9).reshape(-1, 3, 3, 1), bias, relu)
+
+
+def conv1_wgrad64(dz, x, pixels=None):
+    """(dW [Co,9], db [Co]) of conv1 from dZ [B,H,W,Co]; `pixels` = (p0, p1) restricts the sum
+    to the flattened pixels [p0, p1) (one slab row of conv1_wgrad / of the fused dgrad)."""
+    dz = _d(dz)
+    xd = _d(x) / 255.0 if x.dtype == torch.uint8 else _d(x)
+    if pixels is not None:
+        keep = torch.zeros(dz.shape[0] * dz.shape[1] * dz.shape[2], dtype=torch.float64)
+        keep[pixels[0]:pixels[1]] = 1.0
+        dz = dz * keep.view(*dz.shape[:3], 1)
+    dw, db = conv3x3_wgrad64(dz, xd.unsqueeze(-1))
+    return dw.reshape(dw.shape[0], 9), db
+
+
+def fc64(x_nhwc, w_native, bias=None):
+    """logits [B,NO] = flatten_nhwc(x) . w [NO,HW,C] (+ bias), float64."""
+    x, w = _d(x_nhwc), _d(w_native)
+    out = x.reshape(x.shape[0], -1) @ w.reshape(w.shape[0], -1).t()
+    return out if bias is None else out + _d(bias)
+
+
+def fc_block_partials64(y_nhwc, w_native, CH):
+    """The fused conv2 + fc epilogue's partial logits [blocks][2][NO] in float64: block k
+    covers the flattened pixels [k CH, (k + 1) CH); slot 0 is the image of its first pixel,
+    slot 1 the next image; a slot whose image the block does not touch is 0."""
+    y, w = _d(y_nhwc), _d(w_native)
+    B, H, W, C = y.shape
+    HW, NO = H * W, w.shape[0]
+    yf, wf = y.reshape(B * HW, C), w.reshape(NO, HW, C)
+    nblk = -(-B * HW // CH)
+    part = torch.zeros(nblk, 2, NO, dtype=torch.float64)
+    for k in range(nblk):
+        p0, p1 = k * CH, min((k + 1) * CH, B * HW)
+        n0 = p0 // HW
+        for slot in (0, 1):
+            a, b = max(p0, (n0 + slot) * HW), min(p1, (n0 + slot + 1) * HW)
+            if a < b:
+                part[k, slot] = torch.einsum("pc,opc->o", yf[a:b], wf[:, a - (n0 + slot) * HW:b - (n0 + slot) * HW])
+    return part
+
+
+def fc_bwd64(dl, x_nhwc, w_native, scale=1.0, mask=True):
+    """(dX [masked by x > 0], dW * scale, dbias * scale) of fc64, float64."""
+    dl, x, w = _d(dl), _d(x_nhwc), _d(w_native)
+    B = x.shape[0]
+    xf = x.reshape(B, -1)
+    dx = dl @ w.reshape(w.shape[0], -1)
+    if mask:
+        dx = dx * (xf > 0)
+    return dx.view_as(x), scale * (dl.t() @ xf).view_as(w), scale * dl.sum(0)
+
+
+def sgd64(p, g, m, lr, momentum=0.0, dampening=0.0, wd=0.0, nesterov=False, maximize=False, first_step=False):
+    """One torch.optim.SGD step (torch/optim/sgd.py _single_tensor_sgd) in float64:
+    returns (new parameter, new momentum buffer or None)."""
+    p, g, m = _d(p), _d(g), _d(m)
+    d = -g if maximize else g
+    if wd != 0.0:
+        d = d + wd * p
+    buf = None
+    if momentum != 0.0:
+        buf = d.clone() if first_step else momentum * m + (1.0 - dampening) * d
+        d = d + momentum * buf if nesterov else buf
+    return p - lr * d, buf
