@@ -368,8 +368,22 @@ struct SlabSet {
   int* step_ctr = nullptr;    // += 1 at the end (the step's last kernel)
   int sys_store = 0;          // dst with system-scope stores (read by peers over xGMI)
 };
+// gscale != nullptr: the CLIP build of sgd_kernel, which uses g[i] * gscale[0] (one fp32
+// multiply, gscale read from device memory at run time: ClipStats::coef) as the gradient
 void sgd_step(float* p, const float* g, float* mbuf, long n, const SgdArgs& a, const ShadowSet& sh,
-              int* step_ctr, hipStream_t s);
+              int* step_ctr, hipStream_t s, const float* gscale = nullptr);
+// ---- global gradient norm / clip coefficient (grad_norm.hip) --------------------------
+constexpr int GN_THREADS = 256, GN_QUADS = 4, GN_MAX_BLOCKS = 1024;
+struct ClipStats {
+  float total_norm;  // sqrtf(sum of squares) of the last launch
+  float coef;        // min(1, max_norm / (total_norm + 1e-6f))
+  int steps;         // launches so far
+  int clipped;       // launches with coef < 1
+};
+int grad_norm_blocks(long n);  // grid: a function of n only
+// partials: >= grad_norm_blocks(n) floats; ticket: one int, zero before the first launch
+void grad_sqnorm(const float* g, long n, float max_norm, float* partials, int* ticket, ClipStats* out,
+                 hipStream_t s);
 void grad_reduce(const SlabSet& ss, hipStream_t s);
 // row groups (16 or 4) of the fixed summation order grad_reduce uses for this SlabSet
 int grad_reduce_groups(const SlabSet& ss);

@@ -19,17 +19,26 @@ namespace ddp_amd {
 
 // 4 consecutive elements per thread (16-byte loads/stores); n4 = n / 4 quads, the
 // (n % 4) tail is handled by the first threads of block 0.
+// CLIP: the gradient is g[i] * gscale[0] (one fp32 multiply - the rounding of scaling the
+// gradient buffer in place, which is not rewritten); gscale[0] is the clip coefficient that
+// grad_sqnorm_kernel left in device memory, read once per thread, so a captured graph
+// replays with each step's own coefficient.
+template <bool CLIP>
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                   float* __restrict__ mbuf, long n, SgdArgs a,
-                                                  ShadowSet sh, int* __restrict__ step_ctr) {
+                                                  ShadowSet sh, int* __restrict__ step_ctr,
+                                                  const float* __restrict__ gscale) {
   DDP_STAMP(STAMP_K_SGD, 0);
+  float gs = 1.f;
+  if constexpr (CLIP) gs = gscale[0];
   const long n4 = n >> 2;
   const long stride = (long)gridDim.x * blockDim.x;
   for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < n4; q += stride) {
     const long i = q << 2;
     float4 v = reinterpret_cast<const float4*>(p)[q];
     if (a.update) {
-      const float4 d = reinterpret_cast<const float4*>(g)[q];
+      float4 d = reinterpret_cast<const float4*>(g)[q];
+      if constexpr (CLIP) { d.x *= gs; d.y *= gs; d.z *= gs; d.w *= gs; }
       float4 m = {0.f, 0.f, 0.f, 0.f};
       if (a.momentum != 0.f) m = reinterpret_cast<const float4*>(mbuf)[q];
       v.x = sgd_one(v.x, d.x, &m.x, a);
@@ -47,7 +56,9 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
     float v = p[i];
     if (a.update) {
       float m = (a.momentum != 0.f) ? mbuf[i] : 0.f;
-      v = sgd_one(v, g[i], &m, a);
+      float d = g[i];
+      if constexpr (CLIP) d *= gs;
+      v = sgd_one(v, d, &m, a);
       p[i] = v;
       if (a.momentum != 0.f) mbuf[i] = m;
     }
@@ -80,11 +91,14 @@ __global__ void scale_copy_kernel(float* __restrict__ dst, const float* __restri
 }
 
 void sgd_step(float* p, const float* g, float* mbuf, long n, const SgdArgs& a, const ShadowSet& sh,
-              int* step_ctr, hipStream_t s) {
+              int* step_ctr, hipStream_t s, const float* gscale) {
   // 16-byte accesses need 16-byte-aligned buffers (torch allocations and flat views are)
   const long blocks = ((n >> 2) + 255) / 256;
   const unsigned grid = (unsigned)(blocks < 2048 ? (blocks > 0 ? blocks : 1) : 2048);
-  hipLaunchKernelGGL(sgd_kernel, dim3(grid), dim3(256), 0, s, p, g, mbuf, n, a, sh, step_ctr);
+  if (gscale)
+    hipLaunchKernelGGL(sgd_kernel<true>, dim3(grid), dim3(256), 0, s, p, g, mbuf, n, a, sh, step_ctr, gscale);
+  else
+    hipLaunchKernelGGL(sgd_kernel<false>, dim3(grid), dim3(256), 0, s, p, g, mbuf, n, a, sh, step_ctr, gscale);
 }
 
 // empty kernel: the per-launch floor (dispatch + drain + boundary) for kernel benches

@@ -79,6 +79,7 @@ class TrainOptions:
     eval_batch_size: int = 1000       # images per evaluation launch / forward
     eval_only: bool = False           # resume from the newest checkpoint, evaluate, exit
     eval_size: int = 0                # resnet18: images of the synthetic held-out split (0: none)
+    clip_grad_norm: float = 0.0       # global-norm gradient clipping inside opt.step() (0: off; module/CPU path)
 
 
 def validate_options(opts: TrainOptions):
@@ -94,6 +95,21 @@ def validate_options(opts: TrainOptions):
     if opts.model != "resnet18" and opts.eval_size:
         raise ValueError("--eval_size sizes the synthetic held-out split of --model resnet18; simplecnn's "
                          "split is the MNIST test set")
+    if opts.clip_grad_norm < 0:
+        raise ValueError("--clip_grad_norm must be >= 0 (0 = off)")
+    if (opts.device or "").lower() == "gpu":  # the fused engine is certain: refuse before any process starts
+        check_fused_engine_options(opts, opts.engine == "fused" and opts.model == "simplecnn")
+
+
+def check_fused_engine_options(opts: TrainOptions, fused: bool):
+    """Options the fused SimpleCNN engine cannot honour (``fused``: this run uses it)."""
+    if fused and (opts.grad_accum != 1 or opts.global_loss):
+        raise ValueError("--grad_accum / --global_loss need the module path (--engine module) "
+                         "or the CPU path; the fused engine runs one micro-batch per step")
+    if fused and opts.clip_grad_norm:
+        raise ValueError("--clip_grad_norm needs the module path (--engine module) or the CPU path; the "
+                         "fused engine applies SGD inside the kernels that finish each gradient, before "
+                         "the global norm exists")
 
 
 def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
@@ -128,9 +144,7 @@ def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
     else:
         raise ValueError(f"unknown model {opts.model!r}")
     fused = on_gpu and opts.engine == "fused" and opts.model == "simplecnn"
-    if fused and (opts.grad_accum != 1 or opts.global_loss):
-        raise ValueError("--grad_accum / --global_loss need the module path (--engine module) "
-                         "or the CPU path; the fused engine runs one micro-batch per step")
+    check_fused_engine_options(opts, fused)
     if fused:
         fs = flat_space(model)
 
@@ -167,7 +181,10 @@ def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
             print(f"Rank {rank}: Eval split: {tsrc} ({len(edata)} images)", flush=True)
     print(f"Rank {rank}: Dataloader ready", flush=True)
     loss_fn = CrossEntropyLoss()
-    opt = FusedSGD(model, lr=opts.lr, momentum=opts.momentum, weight_decay=opts.weight_decay)
+    # clipping lives in opt.step(): with --grad_accum only the boundary step clips, and under
+    # DDP the norm is of the all-reduced gradient (the same bits, so the same coefficient, on every rank)
+    opt = FusedSGD(model, lr=opts.lr, momentum=opts.momentum, weight_decay=opts.weight_decay,
+                   max_grad_norm=opts.clip_grad_norm or None)
     model.train()
     print(f"Rank {rank}: Loss and Optimizer ready", flush=True)
 
@@ -243,7 +260,8 @@ def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
             ev = run_eval(model, engine, edata, device, opts, rank, world_size, fused)
             _log_eval(rank, epoch, ev)
         _record_metrics(opts, rank, world_size, epoch, nsteps, batch_size, dt,
-                        samples_processed(nsteps, batch_size, len(sampler)), ev)
+                        samples_processed(nsteps, batch_size, len(sampler)), ev,
+                        clip=opt.grad_clip_stats() if opts.metrics_json and rank == 0 else None)
 
         if opts.verify_replicas and world_size > 1:
             verify_replicas(fs, opt, rank, world_size, epoch)
@@ -518,9 +536,11 @@ def samples_processed(nsteps: int, batch: int, samples_per_rank: int) -> int:
     return min(nsteps * batch, samples_per_rank)
 
 
-def _record_metrics(opts, rank, ws, epoch, nsteps, batch, dt, samples, ev=None):
+def _record_metrics(opts, rank, ws, epoch, nsteps, batch, dt, samples, ev=None, clip=None):
     """``samples``: images this rank processed in the epoch (:func:`samples_processed`);
-    ``ev``: the epoch's evaluation totals, when it ran (eval_loss / eval_accuracy keys)."""
+    ``ev``: the epoch's evaluation totals, when it ran (eval_loss / eval_accuracy keys);
+    ``clip``: FusedSGD.grad_clip_stats() with --clip_grad_norm (grad_norm: the last step's
+    norm; clipped_steps: steps clipped so far in this run)."""
     if not opts.metrics_json or rank != 0:
         return
     import json
@@ -532,5 +552,7 @@ def _record_metrics(opts, rank, ws, epoch, nsteps, batch, dt, samples, ev=None):
         rec["eval_loss"], rec["eval_accuracy"] = ev.mean_loss, ev.accuracy
         if ev.correct5 is not None:
             rec["eval_top5"] = ev.top5
+    if clip is not None:
+        rec["grad_norm"], rec["clipped_steps"] = clip["total_norm"], clip["clipped"]
     with open(opts.metrics_json, "a") as f:
         f.write(json.dumps(rec) + "\n")

@@ -197,3 +197,96 @@ def xent_rows_bounds(x, absum, G, labels, gscale, p, rows):
     xl = x[torch.arange(B), labels.long()]
     bl = (D + 64) * U * rows.abs().clamp(min=1.0) + 2 * e_l + 2 * U * (mx.abs() + xl.abs())
     return bd, bl
+
+
+# ------------------------------------------------------------ global gradient norm (clip)
+GN_THREADS, GN_QUADS, GN_MAX_BLOCKS = 256, 4, 1024  # csrc/kernels/launchers.h
+
+
+def grad_norm_blocks(n):
+    """grad_norm_blocks (grad_norm.hip): the grid, a function of n alone."""
+    per = GN_THREADS * GN_QUADS
+    return int(min(max(((n >> 2) + per - 1) // per, 1), GN_MAX_BLOCKS))
+
+
+def sqnorm_passes(n):
+    """Grid-stride passes of grad_sqnorm_kernel over n elements."""
+    per = grad_norm_blocks(n) * GN_THREADS * GN_QUADS
+    return ((n >> 2) + per - 1) // per
+
+
+def _fma32(x32, acc32):
+    """float32 fmaf(x, x, acc): the product of two float32 is exact in extended precision,
+    the sum is rounded once to float32 (as replay_finish)."""
+    x = x32.astype(np.longdouble)
+    return (x * x + acc32.astype(np.longdouble)).astype(np.float32)
+
+
+def _wave_tree(v):
+    """wave_sum (common.h) over the last axis (64 lanes): neighbours, then pairs of those, ..."""
+    while v.shape[-1] > 1:
+        v = (v[..., 0::2] + v[..., 1::2]).astype(np.float32)
+    return v[..., 0]
+
+
+def _block_sum(th):
+    """[blocks][256] thread values -> [blocks]: wave trees, then ((w0 + w1) + w2) + w3."""
+    w = _wave_tree(th.reshape(th.shape[0], 4, 64))
+    return (((w[:, 0] + w[:, 1]).astype(np.float32) + w[:, 2]).astype(np.float32) + w[:, 3]).astype(np.float32)
+
+
+def replay_sqnorm(g32, n=None, drop=None):
+    """The float32 sum of squares of g32[:n] in grad_sqnorm_kernel's documented order
+    (csrc/kernels/grad_norm.hip, header).  drop: index of an element left out (the CPU
+    tests' mutation)."""
+    g32 = np.asarray(g32, dtype=np.float32).reshape(-1)
+    n = g32.size if n is None else int(n)
+    g32 = g32[:n].copy()
+    if drop is not None:
+        g32[drop] = 0.0  # fmaf(0, 0, acc) == acc
+    G = grad_norm_blocks(n)
+    T = G * GN_THREADS
+    n4, passes = n >> 2, sqnorm_passes(n)
+    quads = np.zeros((max(passes, 1) * GN_QUADS * T, 4), dtype=np.float32)  # skipped quads add +0
+    quads[:n4] = g32[:4 * n4].reshape(n4, 4)
+    quads = quads.reshape(max(passes, 1), GN_QUADS, T, 4)
+    acc = np.zeros((GN_QUADS, T, 4), dtype=np.float32)
+    for i in range(passes):
+        acc = _fma32(quads[i], acc)
+    s = ((acc[..., 0] + acc[..., 1]).astype(np.float32) + (acc[..., 2] + acc[..., 3]).astype(np.float32)).astype(np.float32)
+    th = ((s[0] + s[1]).astype(np.float32) + (s[2] + s[3]).astype(np.float32)).astype(np.float32)
+    r = n & 3
+    if r:
+        th[:r] = _fma32(g32[4 * n4:], th[:r])
+    part = np.zeros(4 * GN_THREADS, dtype=np.float32)
+    part[:G] = _block_sum(th.reshape(G, GN_THREADS))
+    p = part.reshape(4, GN_THREADS)
+    tj = (((p[0] + p[1]).astype(np.float32) + p[2]).astype(np.float32) + p[3]).astype(np.float32)
+    return np.float32(_block_sum(tj.reshape(1, GN_THREADS))[0])
+
+
+def clip_coef32(norm32, max_norm):
+    """torch.nn.utils.clip_grad_norm_'s coefficient in float32: min(1, max_norm / (norm + 1e-6))."""
+    q = np.float32(max_norm) / (np.float32(norm32) + np.float32(1e-6))
+    return q if np.isnan(q) else np.float32(min(np.float32(1.0), q))
+
+
+def sqnorm_bound(n, sumsq64):
+    """A-priori bounds of grad_sqnorm_kernel for n elements whose squares sum to sumsq64:
+    (|S - sum x^2|, |total_norm - sqrt(sum x^2)|, relative error of coef where it is < 1).
+
+    Every term x^2 is non-negative and enters through an fma (the product does not round), so
+    with k the longest chain of roundings between a term and S, |S - s| <= gamma_k s,
+    gamma_k = k u / (1 - k u).  k = passes (one accumulator's fma chain) + 2 + 2 (the thread's
+    16 accumulators) + 1 (tail) + 6 + 3 (wave tree, 4 waves) + 3 + 6 + 3 (the last block over
+    the partials) = passes + 26.  sqrtf is correctly rounded: sqrt(s (1 + d)) is within
+    sqrt(s) d / 2 (1 + d) of sqrt(s), then one rounding, so the norm's relative error is at most
+    e_n = (gamma_k / 2 + u)(1 + gamma_k).  The coefficient adds the rounding of norm + 1e-6f, of
+    the constant 1e-6f itself (relative u of a term no larger than the sum) and of the
+    division: e_n + 3 u, times (1 + e_n + 3 u) for the reciprocal.
+    """
+    k = sqnorm_passes(n) + 26
+    gk = k * U / (1.0 - k * U)
+    e_n = (gk / 2 + U) * (1 + gk)
+    e_c = (e_n + 3 * U) * (1 + e_n + 3 * U) / (1 - e_n - 3 * U)
+    return gk * sumsq64, e_n * float(np.sqrt(sumsq64)), e_c

@@ -12,6 +12,14 @@ over the same flat buffers.
 ``param_groups`` keys and order, ``params`` = registration-order indices, and
 ``momentum_buffer`` tensors in the reference layout), so checkpoints stay
 byte-compatible with the reference.
+
+``max_grad_norm`` adds ``torch.nn.utils.clip_grad_norm_`` (norm_type 2) to the step itself:
+``grad_sqnorm_kernel`` (csrc/kernels/grad_norm.hip) leaves the global norm of the flat
+gradient and the coefficient ``min(1, max_norm / (norm + 1e-6))`` in device memory, and the
+CLIP build of ``sgd_kernel`` multiplies every gradient element by it as it reads it.  The
+gradient buffer is not rewritten and nothing reaches the host, so a captured graph replays
+the step with each batch's own coefficient.  Clipping is configured by the constructor only
+and keeps no optimizer state (torch keeps none either): ``state_dict()`` is unchanged.
 """
 from __future__ import annotations
 
@@ -26,9 +34,14 @@ _DEFAULTS = dict(lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=Fals
 class FusedSGD:
     def __init__(self, model: torch.nn.Module, lr: float = 1e-3, momentum: float = 0,
                  dampening: float = 0, weight_decay: float = 0, nesterov: bool = False,
-                 maximize: bool = False):
+                 maximize: bool = False, max_grad_norm: float | None = None):
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        if max_grad_norm is not None and not float(max_grad_norm) > 0:
+            raise ValueError("max_grad_norm must be positive (None: no clipping)")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self._clip_ws = None      # GPU: (partials, ticket, stats), allocated by the first step
+        self._clip_host = None    # CPU: the same four numbers
         self.model = model
         self.flat: FlatSpace = flat_space(model)
         g = dict(_DEFAULTS)
@@ -67,17 +80,59 @@ class FusedSGD:
             shadows = self.shadows
             if fs._bf16 is not None:  # the model's bf16 weight copy, refreshed in the same pass
                 shadows = shadows + [(0, fs.numel, fs._bf16, 1, 0, 0, 0)] + fs.pad4_shadows()
-            native.require().sgd(fs.params, fs.grads, self.momentum_buffer, g["lr"], g["momentum"],
-                                 g["dampening"], g["weight_decay"], g["nesterov"], g["maximize"],
-                                 first, True, shadows)
+            C = native.require()
+            gscale = None
+            if self.max_grad_norm is not None:
+                # the norm runs over the whole buffer: the alignment padding between
+                # parameters is zero and no producer writes it
+                partials, ticket, stats = self._clip_workspace(C)
+                C.grad_sqnorm(fs.grads, self.max_grad_norm, partials, ticket, stats)
+                gscale = stats[1:2]  # ClipStats::coef, read by the kernel at run time
+            C.sgd(fs.params, fs.grads, self.momentum_buffer, g["lr"], g["momentum"],
+                  g["dampening"], g["weight_decay"], g["nesterov"], g["maximize"],
+                  first, True, shadows, gscale)
             fs.mark_bf16_fresh()
         else:
             self._step_torch(first)
         self.steps += 1
 
+    def _clip_workspace(self, C):
+        """Partials, the (zeroed) arrival ticket and the ClipStats words; allocated once, by
+        the first step - GraphedStep's warm-up, so before a capture."""
+        if self._clip_ws is None:
+            dev = self.flat.params.device
+            self._clip_ws = (torch.zeros(C.GRAD_NORM_MAX_BLOCKS, dtype=torch.float32, device=dev),
+                             torch.zeros(1, dtype=torch.int32, device=dev),
+                             torch.zeros(4, dtype=torch.float32, device=dev))
+        return self._clip_ws
+
+    def grad_clip_stats(self) -> dict | None:
+        """``{"total_norm", "coef", "steps", "clipped"}`` of the clipped steps so far (the norm
+        and coefficient are the last step's); one device-to-host read.  ``None`` without
+        ``max_grad_norm`` or before the first step."""
+        if self._clip_host is not None:
+            return dict(self._clip_host)
+        if self._clip_ws is None:
+            return None
+        s = self._clip_ws[2].cpu()
+        i = s.view(torch.int32)
+        return {"total_norm": s[0].item(), "coef": s[1].item(), "steps": int(i[2]), "clipped": int(i[3])}
+
+    def _clip_torch(self, d: torch.Tensor) -> torch.Tensor:
+        """The kernel's rule with torch ops: fp32 norm of the whole flat gradient (summed in
+        float64, rounded once), coef = min(1, max_norm / (norm + 1e-6)) in fp32, d * coef."""
+        norm = d.double().square().sum().sqrt().float()
+        coef = (torch.tensor(self.max_grad_norm, dtype=torch.float32) / (norm + 1e-6)).clamp(max=1.0)
+        h = self._clip_host or {"steps": 0, "clipped": 0}
+        self._clip_host = {"total_norm": norm.item(), "coef": coef.item(), "steps": h["steps"] + 1,
+                           "clipped": h["clipped"] + int(coef.item() < 1.0)}
+        return d * coef
+
     def _step_torch(self, first: bool):
         g = self.param_groups[0]
         p, d = self.flat.params, self.flat.grads
+        if self.max_grad_norm is not None:
+            d = self._clip_torch(d)
         d = -d if g["maximize"] else d.clone()
         if g["weight_decay"] != 0:
             d = d.add(p, alpha=g["weight_decay"])

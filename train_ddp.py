@@ -63,6 +63,9 @@ def parse_args(argv=None):
                         "auto = RCCL under the rccl backend, xGMI under gloo")
     p.add_argument("--grad_accum", type=int, default=1,
                    help="micro-batches per optimizer step (module/CPU path; DDP no_sync)")
+    p.add_argument("--clip_grad_norm", type=float, default=0.0, metavar="X",
+                   help="clip the global gradient L2 norm to X inside the optimizer step, as "
+                        "torch.nn.utils.clip_grad_norm_ (module/CPU path; 0 = off)")
     p.add_argument("--global_loss", action="store_true",
                    help="log the all-reduced mean loss instead of rank 0's local loss (module/CPU path)")
     p.add_argument("--pg_timeout_min", type=float, default=30.0,
@@ -110,6 +113,7 @@ def main(argv=None):
                         graph_module=a.graph_module, verify_replicas=a.verify_replicas,
                         force_allreduce=a.force_allreduce, eval_every=a.eval_every,
                         eval_batch_size=a.eval_batch_size, eval_only=a.eval_only, eval_size=a.eval_size,
+                        clip_grad_norm=a.clip_grad_norm,
                         stall=tuple(float(v) for v in a.stall_at.split(":")) if a.stall_at else None,
                         fault=tuple(int(v) for v in a.fault_at.split(":")) if a.fault_at else None)
     validate_options(opts)
