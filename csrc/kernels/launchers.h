@@ -370,8 +370,12 @@ struct SlabSet {
 };
 // gscale != nullptr: the CLIP build of sgd_kernel, which uses g[i] * gscale[0] (one fp32
 // multiply, gscale read from device memory at run time: ClipStats::coef) as the gradient
+// sched != nullptr: the DLR build, which takes the learning rate from device memory -
+// lr_table[min(sched->t, n_table - 1)] in place of a.lr - and advances sched->t inside the same
+// launch (types.h SchedState), so a captured graph replays each step with its own rate.
 void sgd_step(float* p, const float* g, float* mbuf, long n, const SgdArgs& a, const ShadowSet& sh,
-              int* step_ctr, hipStream_t s, const float* gscale = nullptr);
+              int* step_ctr, hipStream_t s, const float* gscale = nullptr, const float* lr_table = nullptr,
+              int n_table = 0, SchedState* sched = nullptr);
 // ---- global gradient norm / clip coefficient (grad_norm.hip) --------------------------
 constexpr int GN_THREADS = 256, GN_QUADS = 4, GN_MAX_BLOCKS = 1024;
 struct ClipStats {

@@ -67,6 +67,14 @@ struct SgdArgs {
   int nesterov, maximize, first_step, update;
 };
 
+// Device-resident learning-rate schedule state of the DLR build of sgd_kernel: every launch
+// uses lr_table[min(t, n_table - 1)] and advances t; `ticket` counts the blocks that have read
+// t (0 between launches); lr_used is the rate of the last finished launch.
+struct SchedState {
+  int t, ticket;
+  float lr_used;
+};
+
 // diagnostic phase-stamp kernel ids / buffer geometry (common.h DDP_STAMP)
 enum { STAMP_K_CONV_FWD = 0, STAMP_K_FC_BWD = 1, STAMP_K_DGRAD = 2, STAMP_K_WGRAD = 3,
        STAMP_K_GRAD_REDUCE = 4, STAMP_K_SGD = 5, STAMP_K_XENT = 6, STAMP_K_CONV1 = 7,

@@ -80,6 +80,11 @@ class TrainOptions:
     eval_only: bool = False           # resume from the newest checkpoint, evaluate, exit
     eval_size: int = 0                # resnet18: images of the synthetic held-out split (0: none)
     clip_grad_norm: float = 0.0       # global-norm gradient clipping inside opt.step() (0: off; module/CPU path)
+    lr_schedule: str = "none"         # none | cosine | linear | step, per optimizer step (module/CPU path)
+    warmup_steps: int = 0             # linear warm-up from 0.01 * lr over the first N optimizer steps
+    lr_min: float = 0.0               # cosine / linear: the rate the decay ends at
+    lr_step_epochs: int = 0           # step: multiply the rate by lr_gamma every N epochs
+    lr_gamma: float = 0.1
 
 
 def validate_options(opts: TrainOptions):
@@ -97,6 +102,12 @@ def validate_options(opts: TrainOptions):
                          "split is the MNIST test set")
     if opts.clip_grad_norm < 0:
         raise ValueError("--clip_grad_norm must be >= 0 (0 = off)")
+    if opts.lr_schedule not in ("none", "cosine", "linear", "step"):
+        raise ValueError(f"--lr_schedule must be none, cosine, linear or step, got {opts.lr_schedule!r}")
+    if opts.warmup_steps < 0:
+        raise ValueError("--warmup_steps must be >= 0")
+    if opts.lr_schedule == "step" and opts.lr_step_epochs < 1:
+        raise ValueError("--lr_schedule step needs --lr_step_epochs N >= 1")
     if (opts.device or "").lower() == "gpu":  # the fused engine is certain: refuse before any process starts
         check_fused_engine_options(opts, opts.engine == "fused" and opts.model == "simplecnn")
 
@@ -110,6 +121,33 @@ def check_fused_engine_options(opts: TrainOptions, fused: bool):
         raise ValueError("--clip_grad_norm needs the module path (--engine module) or the CPU path; the "
                          "fused engine applies SGD inside the kernels that finish each gradient, before "
                          "the global norm exists")
+    if fused and uses_lr_schedule(opts):
+        raise ValueError("--lr_schedule / --warmup_steps need the module path (--engine module) or the CPU "
+                         "path; the fused engine bakes the learning rate into its kernels' arguments and "
+                         "into its captured step graphs")
+
+
+def uses_lr_schedule(opts: TrainOptions) -> bool:
+    return opts.lr_schedule != "none" or opts.warmup_steps > 0
+
+
+def optimizer_steps_per_epoch(n_batches: int, grad_accum: int = 1, max_steps: int | None = None) -> int:
+    """Optimizer steps of one epoch on a rank: every ``grad_accum`` batches plus the ragged
+    flush (``max_steps`` caps the epoch's batches, as _run_module_epoch does)."""
+    if max_steps is not None:
+        n_batches = min(n_batches, max_steps)
+    return -(-n_batches // grad_accum)
+
+
+def build_lr_schedule(opts: TrainOptions, epochs: int, per_epoch: int):
+    """The run's LRSchedule from the flags, or None for a constant rate (then FusedSGD takes
+    ``lr`` by value, as before).  A pure function of the flags: every rank builds the same table."""
+    if not uses_lr_schedule(opts):
+        return None
+    from ..ops.lr_schedule import LRSchedule
+
+    return LRSchedule(opts.lr, max(1, epochs * per_epoch), opts.lr_schedule, warmup_steps=opts.warmup_steps,
+                      lr_min=opts.lr_min, step_size=opts.lr_step_epochs * per_epoch, gamma=opts.lr_gamma)
 
 
 def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
@@ -183,8 +221,12 @@ def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
     loss_fn = CrossEntropyLoss()
     # clipping lives in opt.step(): with --grad_accum only the boundary step clips, and under
     # DDP the norm is of the all-reduced gradient (the same bits, so the same coefficient, on every rank)
+    # the schedule is indexed by the global optimizer step: a table every rank builds alike from the
+    # flags (no schedule object with the default flags: the by-value sgd_kernel runs)
+    per_epoch = optimizer_steps_per_epoch(len(loader), opts.grad_accum, opts.max_steps)
     opt = FusedSGD(model, lr=opts.lr, momentum=opts.momentum, weight_decay=opts.weight_decay,
-                   max_grad_norm=opts.clip_grad_norm or None)
+                   max_grad_norm=opts.clip_grad_norm or None,
+                   lr_schedule=build_lr_schedule(opts, epochs, per_epoch))
     model.train()
     print(f"Rank {rank}: Loss and Optimizer ready", flush=True)
 
@@ -194,6 +236,13 @@ def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
         print(f"Rank {rank}: No checkpoint found, starting from scratch.", flush=True)
     elif rank == 0:
         print(f"Rank {rank}: Resumed from {path}, starting at epoch {start_epoch}", flush=True)
+    if path is not None and opt.lr_schedule is not None:
+        opt.set_schedule_step(start_epoch * per_epoch)  # the schedule is a function of the step index alone
+        if opt.loaded_lr is not None and opt.loaded_lr != opt.current_lr():  # (rank 0: it read the file)
+            print(f"Rank {rank}: WARNING: the checkpoint's lr {opt.loaded_lr!r} is not this schedule's rate "
+                  f"{opt.current_lr()!r} at step {start_epoch * per_epoch}: the schedule flags, --epochs, "
+                  "--batch_size, --grad_accum, --max_steps and the world size must match the run that "
+                  "wrote the checkpoint", flush=True)
 
     if opts.eval_only:
         if path is None:
@@ -261,7 +310,9 @@ def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
             _log_eval(rank, epoch, ev)
         _record_metrics(opts, rank, world_size, epoch, nsteps, batch_size, dt,
                         samples_processed(nsteps, batch_size, len(sampler)), ev,
-                        clip=opt.grad_clip_stats() if opts.metrics_json and rank == 0 else None)
+                        clip=opt.grad_clip_stats() if opts.metrics_json and rank == 0 else None,
+                        lr=opt.current_lr() if opts.metrics_json and rank == 0 and opt.lr_schedule is not None
+                        else None)
 
         if opts.verify_replicas and world_size > 1:
             verify_replicas(fs, opt, rank, world_size, epoch)
@@ -536,7 +587,7 @@ def samples_processed(nsteps: int, batch: int, samples_per_rank: int) -> int:
     return min(nsteps * batch, samples_per_rank)
 
 
-def _record_metrics(opts, rank, ws, epoch, nsteps, batch, dt, samples, ev=None, clip=None):
+def _record_metrics(opts, rank, ws, epoch, nsteps, batch, dt, samples, ev=None, clip=None, lr=None):
     """``samples``: images this rank processed in the epoch (:func:`samples_processed`);
     ``ev``: the epoch's evaluation totals, when it ran (eval_loss / eval_accuracy keys);
     ``clip``: FusedSGD.grad_clip_stats() with --clip_grad_norm (grad_norm: the last step's
@@ -554,5 +605,7 @@ def _record_metrics(opts, rank, ws, epoch, nsteps, batch, dt, samples, ev=None, 
             rec["eval_top5"] = ev.top5
     if clip is not None:
         rec["grad_norm"], rec["clipped_steps"] = clip["total_norm"], clip["clipped"]
+    if lr is not None:
+        rec["lr"] = lr  # with a schedule: FusedSGD.current_lr() at the end of the epoch, the next step's rate
     with open(opts.metrics_json, "a") as f:
         f.write(json.dumps(rec) + "\n")

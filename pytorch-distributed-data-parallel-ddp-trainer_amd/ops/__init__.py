@@ -6,6 +6,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import reference
+from .lr_schedule import LRSchedule
 from .sgd import FusedSGD
 
 
@@ -23,4 +24,4 @@ class CrossEntropyLoss(nn.Module):
         return F.cross_entropy(logits, labels)
 
 
-__all__ = ["CrossEntropyLoss", "FusedSGD", "reference"]
+__all__ = ["CrossEntropyLoss", "FusedSGD", "LRSchedule", "reference"]

@@ -20,6 +20,15 @@ CLIP build of ``sgd_kernel`` multiplies every gradient element by it as it reads
 gradient buffer is not rewritten and nothing reaches the host, so a captured graph replays
 the step with each batch's own coefficient.  Clipping is configured by the constructor only
 and keeps no optimizer state (torch keeps none either): ``state_dict()`` is unchanged.
+
+``lr_schedule`` (an :class:`~ddp_amd.ops.lr_schedule.LRSchedule`) makes the rate a function of
+the optimizer-step index.  On the GPU the float32 table and a small state block (step index,
+arrival ticket, the rate last used) live in device memory: the DLR build of ``sgd_kernel``
+reads ``table[min(t, n - 1)]`` at run time and advances ``t`` inside the same launch, so eager
+steps and replays of a captured graph share one counter and every step gets its own rate.
+On the CPU the same table is indexed by a host counter.  The schedule adds no checkpoint
+field: ``state_dict()`` keeps its keys, its ``lr`` is the rate the next step will use (as a
+torch scheduler leaves it), and a resumed run restores the index with ``set_schedule_step``.
 """
 from __future__ import annotations
 
@@ -34,7 +43,7 @@ _DEFAULTS = dict(lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=Fals
 class FusedSGD:
     def __init__(self, model: torch.nn.Module, lr: float = 1e-3, momentum: float = 0,
                  dampening: float = 0, weight_decay: float = 0, nesterov: bool = False,
-                 maximize: bool = False, max_grad_norm: float | None = None):
+                 maximize: bool = False, max_grad_norm: float | None = None, lr_schedule=None):
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         if max_grad_norm is not None and not float(max_grad_norm) > 0:
@@ -42,6 +51,10 @@ class FusedSGD:
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self._clip_ws = None      # GPU: (partials, ticket, stats), allocated by the first step
         self._clip_host = None    # CPU: the same four numbers
+        self.lr_schedule = lr_schedule
+        self._sched_ws = None     # GPU: (table, state int32[4] = SchedState t / ticket / lr_used), first step
+        self._sched_t = 0         # CPU: the step index; GPU: the index the state block starts from
+        self.loaded_lr = None     # the lr of the last loaded state dict (with a schedule: not applied)
         self.model = model
         self.flat: FlatSpace = flat_space(model)
         g = dict(_DEFAULTS)
@@ -88,9 +101,11 @@ class FusedSGD:
                 partials, ticket, stats = self._clip_workspace(C)
                 C.grad_sqnorm(fs.grads, self.max_grad_norm, partials, ticket, stats)
                 gscale = stats[1:2]  # ClipStats::coef, read by the kernel at run time
+            # with a schedule every step, eager or captured, runs the DLR build: one device counter
+            sched = self._sched_workspace() if self.lr_schedule is not None else None
             C.sgd(fs.params, fs.grads, self.momentum_buffer, g["lr"], g["momentum"],
                   g["dampening"], g["weight_decay"], g["nesterov"], g["maximize"],
-                  first, True, shadows, gscale)
+                  first, True, shadows, gscale, sched)
             fs.mark_bf16_fresh()
         else:
             self._step_torch(first)
@@ -105,6 +120,46 @@ class FusedSGD:
                              torch.zeros(1, dtype=torch.int32, device=dev),
                              torch.zeros(4, dtype=torch.float32, device=dev))
         return self._clip_ws
+
+    def _sched_workspace(self):
+        """The float32 table and the SchedState words on the device; allocated once, by the
+        first step - GraphedStep's warm-up, so before a capture (as ``_clip_workspace``)."""
+        if self._sched_ws is None:
+            dev = self.flat.params.device
+            self._sched_ws = (self.lr_schedule.table.to(dev),
+                              torch.tensor([self._sched_t, 0, 0, 0], dtype=torch.int32).to(dev))
+        return self._sched_ws
+
+    def _need_schedule(self):
+        if self.lr_schedule is None:
+            raise RuntimeError("this FusedSGD has no lr_schedule")
+
+    def schedule_step(self) -> int:
+        """Optimizer steps the schedule has seen = the index of the next step's rate; on the
+        GPU one device-to-host read of the counter the kernel advances."""
+        self._need_schedule()
+        if self._sched_ws is not None:
+            return int(self._sched_ws[1][0].item())
+        return self._sched_t
+
+    def current_lr(self) -> float:
+        """The rate the next step will use (the constant ``lr`` without a schedule)."""
+        if self.lr_schedule is None:
+            return self.param_groups[0]["lr"]
+        return self.lr_schedule.lr_at(self.schedule_step())
+
+    def set_schedule_step(self, k: int):
+        """Continue the schedule at step ``k`` (resume).  On the GPU a host-to-device write of
+        the counter: never inside a graph capture."""
+        self._need_schedule()
+        k = int(k)
+        if k < 0:
+            raise ValueError("the schedule step must be >= 0")
+        self._sched_t = k
+        if self._sched_ws is not None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("set_schedule_step inside a graph capture")
+            self._sched_ws[1].copy_(torch.tensor([k, 0, 0, 0], dtype=torch.int32))
 
     def grad_clip_stats(self) -> dict | None:
         """``{"total_norm", "coef", "steps", "clipped"}`` of the clipped steps so far (the norm
@@ -143,7 +198,11 @@ class FusedSGD:
             else:
                 buf.mul_(g["momentum"]).add_(d, alpha=1 - g["dampening"])
             d = d.add(buf, alpha=g["momentum"]) if g["nesterov"] else buf
-        p.add_(d, alpha=-g["lr"])
+        lr = g["lr"]
+        if self.lr_schedule is not None:
+            lr = self.lr_schedule.lr_at(self._sched_t)
+            self._sched_t += 1
+        p.add_(d, alpha=-lr)
 
     # ------------------------------------------------------------------ state
     def state_dict(self):
@@ -155,6 +214,8 @@ class FusedSGD:
         groups = []
         for g in self.param_groups:
             d = {k: g[k] for k in _DEFAULTS}
+            if self.lr_schedule is not None:
+                d["lr"] = self.current_lr()
             d["params"] = list(range(len(self._reg_names)))
             groups.append(d)
         return {"state": state, "param_groups": groups}
@@ -164,6 +225,10 @@ class FusedSGD:
         if len(groups) != 1 or len(groups[0]["params"]) != len(self._reg_names):
             raise ValueError("optimizer state_dict does not match this model")
         for k in _DEFAULTS:
+            if k == "lr" and self.lr_schedule is not None:
+                # a checkpoint's lr is a point of the schedule: the base is the constructor's
+                self.loaded_lr = groups[0].get("lr")  # (kept so a resume can check its step index)
+                continue
             if k in groups[0]:
                 self.param_groups[0][k] = groups[0][k]
         st = sd.get("state", {})

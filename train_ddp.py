@@ -66,6 +66,15 @@ def parse_args(argv=None):
     p.add_argument("--clip_grad_norm", type=float, default=0.0, metavar="X",
                    help="clip the global gradient L2 norm to X inside the optimizer step, as "
                         "torch.nn.utils.clip_grad_norm_ (module/CPU path; 0 = off)")
+    p.add_argument("--lr_schedule", choices=["none", "cosine", "linear", "step"], default="none",
+                   help="learning-rate decay per optimizer step over --epochs (after --warmup_steps): cosine or "
+                        "linear down to --lr_min, or times --lr_gamma every --lr_step_epochs epochs; read on the "
+                        "device, so --graph_module replays follow it (module/CPU path)")
+    p.add_argument("--warmup_steps", type=int, default=0, metavar="N",
+                   help="linear warm-up from 0.01 x --lr to --lr over the first N optimizer steps (module/CPU path)")
+    p.add_argument("--lr_min", type=float, default=0.0, metavar="X", help="cosine / linear: the final rate")
+    p.add_argument("--lr_step_epochs", type=int, default=0, metavar="N", help="step: epochs between decays")
+    p.add_argument("--lr_gamma", type=float, default=0.1, metavar="G", help="step: decay factor")
     p.add_argument("--global_loss", action="store_true",
                    help="log the all-reduced mean loss instead of rank 0's local loss (module/CPU path)")
     p.add_argument("--pg_timeout_min", type=float, default=30.0,
@@ -113,7 +122,9 @@ def main(argv=None):
                         graph_module=a.graph_module, verify_replicas=a.verify_replicas,
                         force_allreduce=a.force_allreduce, eval_every=a.eval_every,
                         eval_batch_size=a.eval_batch_size, eval_only=a.eval_only, eval_size=a.eval_size,
-                        clip_grad_norm=a.clip_grad_norm,
+                        clip_grad_norm=a.clip_grad_norm, lr_schedule=a.lr_schedule,
+                        warmup_steps=a.warmup_steps, lr_min=a.lr_min, lr_step_epochs=a.lr_step_epochs,
+                        lr_gamma=a.lr_gamma,
                         stall=tuple(float(v) for v in a.stall_at.split(":")) if a.stall_at else None,
                         fault=tuple(int(v) for v in a.fault_at.split(":")) if a.fault_at else None)
     validate_options(opts)
