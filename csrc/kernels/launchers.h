@@ -457,6 +457,10 @@ struct BwdXar {
   int* err = nullptr;         // 4: a completion wait timed out
 };
 constexpr int XAR_ERR = 4;
+// the other codes of the step's wait-timeout word (the engine's sync_err; sticky)
+constexpr int RED_ERR = 2;      // the fused slab reduction's arrival count (conv3x3_bwd red_err)
+constexpr int FWD_DZ_ERR = 3;   // the level-3 forward's granule sweep (FwdDz::err)
+constexpr int HEAD_ERR = 5;     // the step head's forward waiting for a bucket's all-reduce
 // Both buckets' all-reduces in ONE launch (engine dist_mode 3, behind the conv backward on
 // the compute stream): blocks [0, nblk0) run bucket 0, [nblk0, nblk0 + nblk1) bucket 1,
 // concurrently; the waits / expected counts of BwdXar are unused, the last block advances

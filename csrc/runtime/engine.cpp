@@ -28,8 +28,15 @@
 //   level 1: conv1 recomputed inside conv2 fwd / dgrad / wgrad, cross-entropy in the
 //            fc_bwd prologue, optimizer in the epilogues, the slab reduction inside the
 //            conv backward: 3 kernels (forward -> fc_bwd -> conv backward);
-//   f32 = 1 (--dtype fp32): the same chains with exact fp32 operands (launch_step_f32): level 3
-//            with both conv backward roles channel-split at two blocks per CU, or level 1.
+//   f32 = 1 (--dtype fp32): the same chains with exact fp32 operands: level 3 with both conv
+//            backward roles channel-split at two blocks per CU, or level 1.
+//
+// There is one step function, launch_step_t<T>, for the bf16 operands and the fp32 ones
+// (StepOperands; level 0 and the dist_mode 4 step head are bf16 only).  It reads as forward ->
+// fc backward set-up -> slab set -> conv backward + bucket all-reduces -> optimizer, each
+// block filling one launcher struct (make_c1src, make_fwd_dz, make_fc_extras, make_slabs).
+// Which chain a step runs is decided in one place, plan_step (step_plan.h, host-only and
+// unit-tested); nothing here derives a chain boolean of its own.
 //
 // Buckets follow the reference DDP's rebuilt layout by default:
 // bucket 0 = [fl.weight, fl.bias] (2.0 MB), bucket 1 = [net.2.*, net.0.*] (74 KB); any
@@ -38,6 +45,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "runtime/runtime.h"
 
@@ -120,300 +128,229 @@ void SimpleCNNEngine::synchronize() {
   DDP_HIP_CHECK(hipStreamSynchronize(cs_));
   if (const int e = sync_error()) {
     throw std::runtime_error(std::string("engine: an in-launch hand-off wait timed out (") +
-                             (e == 2 ? "fused slab reduction" : e == XAR_ERR ? "in-launch all-reduce"
-                                      : e == 5 ? "dist_mode 4 step head: forward waiting for the bucket all-reduce"
-                                               : "level-3 forward dZ2") +
+                             (e == RED_ERR ? "fused slab reduction" : e == XAR_ERR ? "in-launch all-reduce"
+                              : e == HEAD_ERR ? "dist_mode 4 step head: forward waiting for the bucket all-reduce"
+                                              : "level-3 forward dZ2") +
                              "); results invalid");
   }
 }
 
 bool SimpleCNNEngine::sync_ok_for_xar() const { return b_.sync_flags != nullptr && b_.sync_err != nullptr; }
 
-bool SimpleCNNEngine::level3_active(int batch) {
-  if (cfg_.fuse_level < 3 || !b_.sync_flags || !b_.sync_err) return false;
-  if (batch <= 0 || batch > cfg_.max_batch) return false;
-  signed char& f = l3_fits_[batch];
-  if (f < 0)
-    f = conv3x3_fwd_dz_fits(batch, cfg_.H, cfg_.W, cfg_.pxt_fwd, cfg_.f32 ? 4 : 2) && cfg_.C1 == 32 && cfg_.C2 == 64
-            ? 1 : 0;
-  return f == 1;
+StepPlan SimpleCNNEngine::plan(int batch) {
+  StepFacts f;
+  f.xgmi = xgmi_ != nullptr;
+  f.xgmi_world = xgmi_ ? xgmi_->world() : 1;
+  f.comm = comm_ != nullptr;
+  f.comm_world = comm_ ? comm_->world() : 1;
+  f.sync_flags = b_.sync_flags != nullptr;
+  f.sync_err = b_.sync_err != nullptr;
+  // (the residency query: once per batch size, and only for an engine built for level 3)
+  if (cfg_.fuse_level >= 3 && batch > 0 && batch <= cfg_.max_batch) {
+    signed char& fit = l3_fits_[batch];
+    if (fit < 0)
+      fit = conv3x3_fwd_dz_fits(batch, cfg_.H, cfg_.W, cfg_.pxt_fwd, cfg_.f32 ? 4 : 2) && cfg_.C1 == 32 &&
+                    cfg_.C2 == 64
+                ? 1 : 0;
+    f.l3_fits = fit == 1;
+  }
+  f.fc_role_ok = conv3x3_bwd_fc_role_ok(cfg_.H, cfg_.W, cfg_.C1, cfg_.C2, cfg_.pxt_dgrad, cfg_.wgrad_split);
+  f.xar_plan_ok = xar_plan_ok_;
+  return plan_step(cfg_, f, batch);
 }
 
-bool SimpleCNNEngine::overlap_active() {
-  const bool use_x = xgmi_ && (xgmi_->world() > 1 || cfg_.force_allreduce);
-  return cfg_.dist_mode == 4 && !cfg_.f32 && use_x && pair_plan_ok_ && cfg_.fuse_level >= 3 && cfg_.l3_fc_role &&
-         cfg_.pxt_fwd == 1 && level3_active(cfg_.max_batch) &&
-         conv3x3_bwd_fc_role_ok(cfg_.H, cfg_.W, cfg_.C1, cfg_.C2, cfg_.pxt_dgrad, cfg_.wgrad_split);
+ShadowSet SimpleCNNEngine::shadow_set(bool plain_fc) const {
+  // (make_xar finds the device copy of a step's all-reduce arguments by their bytes, this set
+  // among them: keep the order of the regions)
+  const int HW = cfg_.H * cfg_.W, C1 = cfg_.C1, C2 = cfg_.C2;
+  const long n_w2 = (long)C2 * 9 * C1, n_fc = (long)cfg_.NO * HW * C2;
+  ShadowSet sh{};
+  if (cfg_.f32) {
+    sh.r[0] = ShadowRegion{b_.off_w2, n_w2, nullptr, SHADOW_F32_TAPT, C2, 9, C1, b_.w2t_f32};
+    sh.r[1] = ShadowRegion{b_.off_wfc, n_fc, nullptr, SHADOW_F32_FCFRAG, HW, C2, 0, b_.wfc_frag32};
+    sh.count = 2;
+    return sh;
+  }
+  sh.r[0] = ShadowRegion{b_.off_w2, n_w2, b_.w2_bf16, SHADOW_BF16, 0, 0, 0};
+  sh.r[1] = ShadowRegion{b_.off_w2, n_w2, b_.w2t_bf16, SHADOW_BF16_TAPT, C2, 9, C1};
+  sh.r[2] = ShadowRegion{b_.off_wfc, n_fc, b_.wfc_frag, SHADOW_BF16_FCFRAG, HW, C2, 0};
+  sh.r[3] = ShadowRegion{b_.off_wfc, n_fc, b_.wfc_bf16, SHADOW_BF16, 0, 0, 0};
+  sh.count = plain_fc ? 4 : 3;
+  return sh;
 }
 
 void SimpleCNNEngine::refresh_shadows() {
-  SgdArgs a{0.f, 0.f, 0.f, 0.f, 0, 0, 0, /*update=*/0};
-  ShadowSet sh{};
-  const long n_w2 = (long)cfg_.C2 * 9 * cfg_.C1;
-  if (cfg_.f32) {
-    sh.r[0] = ShadowRegion{b_.off_w2, n_w2, nullptr, SHADOW_F32_TAPT, cfg_.C2, 9, cfg_.C1, b_.w2t_f32};
-    sh.r[1] = ShadowRegion{b_.off_wfc, (long)cfg_.NO * cfg_.H * cfg_.W * cfg_.C2, nullptr, SHADOW_F32_FCFRAG,
-                           cfg_.H * cfg_.W, cfg_.C2, 0, b_.wfc_frag32};
-    sh.count = 2;
-    sgd_step(b_.params, b_.grads, nullptr, b_.n_params, a, sh, nullptr, cs_);
-    DDP_HIP_CHECK(hipGetLastError());
-    return;
-  }
-  sh.r[0] = ShadowRegion{b_.off_w2, n_w2, b_.w2_bf16, SHADOW_BF16, 0, 0, 0};
-  sh.r[1] = ShadowRegion{b_.off_w2, n_w2, b_.w2t_bf16, SHADOW_BF16_TAPT, cfg_.C2, 9, cfg_.C1};
-  sh.r[2] = ShadowRegion{b_.off_wfc, (long)cfg_.NO * cfg_.H * cfg_.W * cfg_.C2, b_.wfc_bf16,
-                         SHADOW_BF16, 0, 0, 0};
-  sh.r[3] = ShadowRegion{b_.off_wfc, (long)cfg_.NO * cfg_.H * cfg_.W * cfg_.C2, b_.wfc_frag,
-                         SHADOW_BF16_FCFRAG, cfg_.H * cfg_.W, cfg_.C2, 0};
-  sh.count = 4;
-  sgd_step(b_.params, b_.grads, nullptr, b_.n_params, a, sh, nullptr, cs_);
+  const SgdArgs a{0.f, 0.f, 0.f, 0.f, 0, 0, 0, /*update=*/0};
+  sgd_step(b_.params, b_.grads, nullptr, b_.n_params, a, shadow_set(true), nullptr, cs_);
   DDP_HIP_CHECK(hipGetLastError());
 }
 
-void SimpleCNNEngine::launch_step(int B, int stride, bool first_momentum_step, unsigned parts) {
-  if (cfg_.f32) {
-    if (parts != PART_ALL) throw std::runtime_error("engine: the fp32 step runs whole (no step-head merge)");
-    launch_step_f32(B, stride, first_momentum_step);
-    return;
-  }
-  const int H = cfg_.H, W = cfg_.W, HW = H * W, C1 = cfg_.C1, C2 = cfg_.C2, NO = cfg_.NO;
-  if (B <= 0 || B > cfg_.max_batch) throw std::runtime_error("engine: bad batch size");
-  const bool use_x = xgmi_ && (xgmi_->world() > 1 || cfg_.force_allreduce);
-  const bool dist = use_x || (comm_ && (comm_->world() > 1 || cfg_.force_allreduce));
-  const float inv_ws = 1.f / (float)cfg_.world;
-  BatchIdx bi{b_.idx, b_.step_ctr, stride, 0};
-  bi.n_idx = b_.n_idx;
-  bi.n_rows = b_.n_rows;
-  float* P = b_.params;
-  float* G = b_.grads;
+namespace {
 
-  const bool f1 = cfg_.fuse_level >= 1;
-  // level 1: the forward gathers the batch (step counter -> index list -> dataset row)
-  // and writes it compactly (xb images, yb labels); every later kernel of the step reads
-  // the compact copy with the identity index (no dependent lookup chain).
+// What the bf16 step (T = bf16_t: shadows of the fp32 master) and the exact-fp32 step
+// (T = float: the master itself and its two re-ordered copies) hand to the same launchers.
+template <typename T>
+struct StepOperands {
+  const T* w2;        // conv2 weight: the forward's operand
+  const T* w2t;       // ... and its [tap][ci][co] copy: the data gradient's operand
+  T* a2;              // ReLU2 output
+  T* dz2;             // dZ2
+  const T* wfc_frag;  // fc weight in fragment order: the forward's fused fc epilogue
+  const T* wfc;       // fc weight, plain: the level-1 fc backward's dX operand
+  T* a1;              // stored conv1 output (level 0, store_a1); the fp32 step never stores it
+  ShadowSet sh;       // the copies above that an optimizer pass of this step refreshes
+};
+
+template <typename T>
+StepOperands<T> step_operands(const EngineBuffers& b, const ShadowSet& sh) {
+  if constexpr (std::is_same<T, float>::value)
+    return {b.params + b.off_w2, b.w2t_f32, b.a2_f32, b.dz2_f32, b.wfc_frag32, b.params + b.off_wfc, nullptr, sh};
+  else
+    return {b.w2_bf16, b.w2t_bf16, b.a2, b.dz2, b.wfc_frag, b.wfc_bf16, b.a1, sh};
+}
+
+}  // namespace
+
+void SimpleCNNEngine::launch_step(int B, int stride, bool first_momentum_step, unsigned parts) {
+  if (cfg_.f32)
+    launch_step_t<float>(B, stride, first_momentum_step, parts);
+  else
+    launch_step_t<bf16_t>(B, stride, first_momentum_step, parts);
+}
+
+// Level 1 up: the forward gathers the batch (step counter -> index list -> dataset row) and
+// writes it compactly (xb images, yb labels); every later kernel of the step reads the
+// compact copy with the identity index (no dependent lookup chain).
+C1Src SimpleCNNEngine::make_c1src(int B, int stride, const StepPlan& pl) const {
   C1Src c1;
   c1.x = b_.images;
-  c1.bi = bi;
-  c1.w = P + b_.off_w1;
-  c1.b = P + b_.off_b1;
+  c1.bi = BatchIdx{b_.idx, b_.step_ctr, stride, 0};
+  c1.bi.n_idx = b_.n_idx;
+  c1.bi.n_rows = b_.n_rows;
+  c1.w = b_.params + b_.off_w1;
+  c1.b = b_.params + b_.off_b1;
   c1.xb_out = b_.xb;
   c1.yb_out = b_.yb;
   c1.labels = b_.labels;
   if (cfg_.store_a1) c1.a1_out = b_.a1;
-  const bool l3 = level3_active(B);
-  const bool fred = f1 && cfg_.fuse_reduce && b_.sync_flags;  // grad_reduce inside the conv bwd
-  const long n_fc = (long)NO * HW * C2;
-  // dist_mode 3 on any chain (level 1 too: the same-GPU multi-rank rehearsals run level 1):
-  // one stream, both buckets in one launch behind the conv backward
-  const bool pair_mode = dist && use_x && f1 && cfg_.dist_mode >= 3 && sync_ok_for_xar();
-  if (fred || l3 || pair_mode) {  // the forward resets the step's hand-off counters
-    const int nfwd = conv3x3_dgrad_blocks(B, H, W, cfg_.pxt_fwd);
-    const int nsync = SYNC_RED_INTS + ((l3 || pair_mode) ? L3_FC_INTS : 0);
+  if (pl.fred || pl.l3 || pl.pair_mode) {  // the forward resets the step's hand-off counters
+    const int nfwd = conv3x3_dgrad_blocks(B, cfg_.H, cfg_.W, cfg_.pxt_fwd);
+    const int nsync = SYNC_RED_INTS + ((pl.l3 || pl.pair_mode) ? L3_FC_INTS : 0);
     c1.zero_i32 = b_.sync_flags;
     c1.zero_per_block = (nsync + nfwd - 1) / nfwd;
     c1.zero_total = nsync;
   }
-  if (!l3 && plain_stale_) {
-    // the plain bf16 fc shadow (read by the level-1 fc backward) was not refreshed by the
-    // level-3 steps before this one: re-derive every shadow from the fp32 master first
-    refresh_shadows();
-    plain_stale_ = false;
-  }
-  // level 3: the forward also writes dZ2 (per-image in-launch sweep of the partial-logit granules)
-  FwdDz dzo;
-  if (l3) {
-    dzo.dz2 = b_.dz2;
-    dzo.gran = gran_;
-    dzo.gen = gen_;
-    dzo.fc_bias = P + b_.off_bfc;
-    dzo.gscale = 1.f / (float)B;
-    dzo.err = b_.sync_err;
-    dzo.dl_out = b_.dlogits;     // dL rows + per-row losses: the fc backward reads them
-    dzo.loss_rows = b_.loss_rows;
-  }
-  // level 3, single process: the fc weight gradient runs as a third role of the conv
-  // backward launch (2 kernels per step); at world size > 1 it runs as its own light kernel
-  // before it (the fc bucket's all-reduce then overlaps the conv backward)
-  // dist_mode 2 (xGMI): the same fc role inside the conv backward at world size > 1, its
-  // gradient all-reduced in-launch (make_xar / BwdXar)
-  const bool xar_mode = dist && use_x && l3 &&
-                        ((cfg_.dist_mode == 2 && xar_plan_ok_) || cfg_.dist_mode >= 3);
-  // the one-stream chains: fc weight gradient (role or kernel) -> conv backward -> the bucket
-  // all-reduces on cs_ (in-launch: dist_mode 2; one pair launch: dist_mode 3 / 4)
-  const bool one_stream = xar_mode || pair_mode;
-  const bool fc_role = l3 && (!dist || xar_mode) && cfg_.l3_fc_role &&
-                       conv3x3_bwd_fc_role_ok(H, W, C1, C2, cfg_.pxt_dgrad, cfg_.wgrad_split);
-  // dist_mode 4 (the step head): mode 3's chain, but the step counter advances in the conv
-  // backward's fc role (after it read the loss index) instead of the pair launch, so that the
-  // pair launch can carry the NEXT step's forward (which reads the counter for its batch)
-  const bool ov = dist && use_x && l3 && fc_role && cfg_.dist_mode == 4;
-  if ((parts & (PART_HEAD | PART_AR)) && !ov && parts != PART_ALL)
-    throw std::runtime_error("engine: a split step needs the dist_mode 4 chain");
-  const C1Src* pc1 = f1 ? &c1 : nullptr;
-  BatchIdx bid{nullptr, nullptr, 0, 0};
-  bid.n_rows = B;
-  C1Src c1b;
-  c1b.x = b_.xb;
-  c1b.bi = bid;
-  c1b.w = c1.w;
-  c1b.b = c1.b;
+  return c1;
+}
 
-  // every bf16 shadow the chain reads; a bucket's fused SGD refreshes the ones inside its
-  // range (level 3 never reads the plain fc shadow: plain_stale_ re-derives it on a switch)
-  const long n_w2s = (long)C2 * 9 * C1;
-  ShadowSet sh_all{};
-  sh_all.r[0] = ShadowRegion{b_.off_w2, n_w2s, b_.w2_bf16, SHADOW_BF16, 0, 0, 0};
-  sh_all.r[1] = ShadowRegion{b_.off_w2, n_w2s, b_.w2t_bf16, SHADOW_BF16_TAPT, C2, 9, C1};
-  sh_all.r[2] = ShadowRegion{b_.off_wfc, n_fc, b_.wfc_frag, SHADOW_BF16_FCFRAG, HW, C2, 0};
-  sh_all.r[3] = ShadowRegion{b_.off_wfc, n_fc, b_.wfc_bf16, SHADOW_BF16, 0, 0, 0};
-  sh_all.count = l3 ? 3 : 4;
-  // ---- forward (PART_HEAD: in one launch with the previous step's bucket all-reduces)
-  const SgdArgs sa{cfg_.lr, cfg_.momentum, cfg_.dampening, cfg_.weight_decay, cfg_.nesterov,
-                   cfg_.maximize, first_momentum_step ? 1 : 0, 1};
-  float* M = b_.momentum;  // null when momentum == 0
-  bool head_used = false;
-  if (parts & PART_HEAD) {
-    // the previous step's pair (its fused SGD writes this step's parameters write-through)
-    // + this step's forward; two launches (same bits) when the merged grid does not fit
-    if (first_momentum_step) throw std::runtime_error("engine: the step head runs the steady-state SGD only");
-    // the head's fused SGD refreshes the shadows its forward reads (conv2 bf16, fc fragment
-    // order); the conv2 [tap][ci][co] copy (the next backward's) is written after the conv
-    // bucket's count (FwdMerge late).  The same bytes as sh_all, in two passes.
-    // Only when the whole conv2 weight lies in the one-shot conv-stage bucket: its blocks
-    // then rewrite exactly the quads they updated (no wait on another block); any other plan
-    // refreshes every shadow in the SGD pass as before.
-    ShadowSet sh_head = sh_all, late{};
-    if (late_shadow_ok(b_.off_w2, n_w2s)) {
-      sh_head.r[1] = sh_all.r[2];
-      sh_head.count = 2;
-      late.r[0] = sh_all.r[1];
-      late.count = 1;
-    }
-    BwdXar hx;
-    int* mc = b_.sync_flags + L3_HEAD_OFF;
-    if (cfg_.pxt_fwd == 1 && B == cfg_.max_batch) {
-      if (!make_xar(hx, sa, M, sh_head)) throw std::runtime_error("engine: the step head needs the pair plan");
-      hx.step_ctr = nullptr;  // (advanced by the fc role)
-      head_used = conv3x3_step_head(hx, mc, mc + FWD_DZ_CNT_STRIDE, b_.w2_bf16, P + b_.off_b2, b_.a2, B,
-                                    b_.wfc_frag, b_.fc_part, c1, dzo, b_.sync_err, cs_, &late);
-    }
-    if (!head_used) {
-      if (!make_xar(hx, sa, M, sh_all)) throw std::runtime_error("engine: the step head needs the pair plan");
-      hx.step_ctr = nullptr;
-      xgmi_allreduce_pair(hx, cs_);
-    }
-    DDP_HIP_CHECK(hipGetLastError());
-  }
-  if ((parts & PART_FWD) || ((parts & PART_HEAD) && !head_used)) {
-    if (!f1) conv1_fwd(b_.images, true, bi, P + b_.off_w1, P + b_.off_b1, b_.a1, B, H, W, C1, cs_);
-    conv3x3_fwd(f1 ? nullptr : b_.a1, b_.w2_bf16, P + b_.off_b2, b_.a2, B, H, W, C1, C2, true,
-                b_.wfc_frag, b_.fc_part, NO, cfg_.pxt_fwd, cs_, pc1, l3 ? &dzo : nullptr);
-  }
-  if (parts & (PART_FWD | PART_HEAD)) last_head_ = head_used;
-  if (head_used && capturing_) graph_heads_ += 1;
-  if (!(parts & (PART_BWD | PART_AR))) return;
-  // ---- loss + fc backward (bucket 0)
-  if (!f1)
-    xent_rows(b_.fc_part, HW, 64 * cfg_.pxt_fwd, P + b_.off_bfc, NO, B, b_.labels, bi, b_.dlogits,
-              b_.loss_rows, 1.f / (float)B, cs_);
+// Level 3: the forward also writes dZ2 (per-image in-launch sweep of the partial-logit granules)
+FwdDz SimpleCNNEngine::make_fwd_dz(int B) const {
+  FwdDz dz;
+  if (cfg_.f32) dz.dz2_f32 = b_.dz2_f32;
+  else dz.dz2 = b_.dz2;
+  dz.gran = gran_;
+  dz.gen = gen_;
+  dz.fc_bias = b_.params + b_.off_bfc;
+  dz.gscale = 1.f / (float)B;
+  dz.err = b_.sync_err;
+  dz.dl_out = b_.dlogits;  // dL rows + per-row losses: the fc backward reads them
+  dz.loss_rows = b_.loss_rows;
+  return dz;
+}
+
+// The fc weight gradient's extras, for fc_bwd and for the conv backward's fc role alike.
+FcBwdExtras SimpleCNNEngine::make_fc_extras(int B, const StepPlan& pl, const SgdArgs& sa) const {
+  float* P = b_.params;
+  float* M = b_.momentum;
   FcBwdExtras ex;
-  ex.dbias = G + b_.off_bfc;  // fc bias grad (bucket 0), prescaled
-  ex.dbias_scale = inv_ws;
-  ex.loss_rows = b_.loss_rows;
+  ex.dbias = b_.grads + b_.off_bfc;  // fc bias grad (bucket 0), prescaled
+  ex.dbias_scale = 1.f / (float)cfg_.world;
   ex.loss_out = b_.loss_hist;  // per-epoch history, indexed by the step counter
   ex.step_ctr = b_.step_ctr;
-  if (f1) {
-    ex.loss_rows = nullptr;
-    ex.part = b_.fc_part;
-    ex.HW = HW;
+  // the row losses come from xent_rows (level 0) or the forward (level 3); level 1 computes
+  // them with dL in the cross-entropy prologue of every block (ex.part: the one field that
+  // selects it - the ones after it are read by that prologue only)
+  ex.loss_rows = (pl.l3 || !pl.f1) ? b_.loss_rows : nullptr;
+  if (pl.f1) {
+    ex.part = pl.l3 ? nullptr : b_.fc_part;
+    ex.HW = cfg_.H * cfg_.W;
     ex.CH = 64 * cfg_.pxt_fwd;
     ex.fc_bias = P + b_.off_bfc;
     ex.labels32 = b_.yb;
-    ex.bi = bid;
+    ex.bi = BatchIdx{nullptr, nullptr, 0, 0};
+    ex.bi.n_rows = B;
     ex.gscale = 1.f / (float)B;
   }
-  // single-process steps: no all-reduce separates a gradient from its update, so the
-  // optimizer runs in the epilogues of the kernels that finish each gradient (fc weight:
-  // fc_bwd; convs + fc bias: grad_reduce) and the separate SGD pass disappears
-  const bool fopt = !dist && cfg_.fuse_opt;
-  const long n_w2 = (long)C2 * 9 * C1, w2row = n_w2 + C2;
-  ex.sys_store = use_x ? 1 : 0;  // bucket 0 is read by the peers over xGMI
-  if (fopt) {
+  ex.sys_store = pl.use_x ? 1 : 0;  // bucket 0 is read by the peers over xGMI
+  if (pl.fopt) {
+    // each block / wave updates only the fc columns it alone reads: race free in place
+    // (the fc weight gradient is consumed in registers and not stored)
     ex.sgd = sa;
     ex.p_w = P + b_.off_wfc;
     ex.m_w = M ? M + b_.off_wfc : nullptr;
-    ex.sh_plain = b_.wfc_bf16;
-    ex.sh_frag = b_.wfc_frag;
-    ex.frag_HW = HW;
-    ex.frag_C = C2;
+    if (cfg_.f32) {
+      ex.sh_frag32 = b_.wfc_frag32;
+    } else {
+      // level 3 never reads the plain bf16 fc shadow (stale until plain_stale_ refreshes it)
+      ex.sh_plain = pl.l3 ? nullptr : b_.wfc_bf16;
+      ex.sh_frag = b_.wfc_frag;
+    }
+    ex.frag_HW = cfg_.H * cfg_.W;
+    ex.frag_C = cfg_.C2;
   }
-  // (fused optimizer: the fc weight gradient is consumed in registers and not stored)
-  BwdFc fcr;  // the conv backward's fc role (fc_role)
-  std::function<void(hipStream_t)> fc_launch;  // the fc weight-gradient kernel, when not a role
-  if (l3) {
-    // level 3: no dZ2 and no cross-entropy prologue here (the forward wrote dZ2, dL, losses)
-    ex.part = nullptr;
-    ex.loss_rows = b_.loss_rows;
+  if (pl.l3) {
     ex.gen_inc = gen_;  // the next forward's granule tags: a new generation
-    if (ov) {           // dist_mode 4: re-arm the step head's two bucket-done counters
+    if (pl.ov) {        // dist_mode 4: re-arm the step head's two bucket-done counters
       ex.zero_i32 = b_.sync_flags + L3_HEAD_OFF;
       ex.n_zero = 2;
       ex.zero_stride = FWD_DZ_CNT_STRIDE;
     }
-    if (fc_role) {
-      // inside the conv backward launch: block 0 of the fc role owns the fc bias, the loss
-      // and the step counter (nothing else in the launch reads them)
-      if (fopt) {
-        ex.p_b = P + b_.off_bfc;
-        ex.m_b = M ? M + b_.off_bfc : nullptr;
-        ex.step_inc = b_.step_ctr;
-      }
-      if (ov) ex.step_inc = b_.step_ctr;
-      ex.sh_plain = nullptr;  // level 3 never reads the plain bf16 fc shadow (stale until refreshed)
-      fcr.a2 = b_.a2;
-      fcr.dl = b_.dlogits;
-      fcr.dW = fopt ? nullptr : G + b_.off_wfc;
-      fcr.scale = inv_ws;
-      fcr.K = (long)HW * C2;
-      fcr.ex = ex;
-    } else {
-      ex.sh_plain = nullptr;
-      fc_launch = [&](hipStream_t s) {
-        fc_bwd(b_.dlogits, b_.a2, nullptr, nullptr, fopt ? nullptr : G + b_.off_wfc, inv_ws, B, (long)HW * C2, NO,
-               /*mask=*/true, s, ex);
-      };
-    }
-    plain_stale_ = true;
-  } else {
-    fc_launch = [&](hipStream_t s) {
-      fc_bwd(b_.dlogits, b_.a2, b_.wfc_bf16, b_.dz2, fopt ? nullptr : G + b_.off_wfc, inv_ws, B,
-             (long)HW * C2, NO, /*mask=*/true, s, ex);
-    };
   }
-  // ---- conv backward (bucket 1) + the slab reduction (fused into it, or grad_reduce)
+  if (pl.fc_role) {
+    // inside the conv backward launch: block 0 of the fc role owns the fc bias, the loss
+    // and the step counter (nothing else in the launch reads them)
+    if (pl.fopt) {
+      ex.p_b = P + b_.off_bfc;
+      ex.m_b = M ? M + b_.off_bfc : nullptr;
+    }
+    if (pl.fopt || pl.ov) ex.step_inc = b_.step_ctr;
+  }
+  return ex;
+}
+
+// The split-K weight-gradient slabs of the conv backward and where their fixed-order sums go
+// (the slab reduction: fused into the conv backward, or grad_reduce).
+SlabSet SimpleCNNEngine::make_slabs(int B, const StepPlan& pl, const SgdArgs& sa) const {
+  const int C1 = cfg_.C1, C2 = cfg_.C2, NO = cfg_.NO;
+  const long n_w2 = (long)C2 * 9 * C1, w2row = n_w2 + C2;
+  const float inv_ws = 1.f / (float)cfg_.world;
+  float* G = b_.grads;
   SlabSet ss{};
-  const int wblk = conv3x3_wgrad_blocks(B, H, cfg_.wgrad_rows);
+  const int wblk = conv3x3_wgrad_blocks(B, cfg_.H, cfg_.wgrad_rows);
   ss.s[0] = SlabSeg{b_.w2slab, w2row, 0, n_w2, wblk, G + b_.off_w2, inv_ws};
   ss.s[1] = SlabSeg{b_.w2slab, w2row, n_w2, (long)C2, wblk, G + b_.off_b2, inv_ws};
-  const int dblk = conv3x3_dgrad_blocks(B, H, W, cfg_.pxt_dgrad);
+  const int dblk = conv3x3_dgrad_blocks(B, cfg_.H, cfg_.W, cfg_.pxt_dgrad);
   ss.s[2] = SlabSeg{b_.w1slab, 320, 0, (long)C1 * 9, dblk, G + b_.off_w1, inv_ws};
   ss.s[3] = SlabSeg{b_.w1slab, 320, (long)C1 * 9, (long)C1, dblk, G + b_.off_b1, inv_ws};
   ss.count = 4;
-  if (fopt) {
+  if (pl.fopt) {
     auto opt = [&](SlabSeg& sg, long off) {
-      sg.p = P + off;
-      sg.m = M ? M + off : nullptr;
+      sg.p = b_.params + off;
+      sg.m = b_.momentum ? b_.momentum + off : nullptr;
     };
     opt(ss.s[0], b_.off_w2);
-    ss.s[0].sh = b_.w2_bf16;
-    ss.s[0].sh_t = b_.w2t_bf16;
+    if (cfg_.f32) {
+      ss.s[0].sh_t32 = b_.w2t_f32;
+    } else {
+      ss.s[0].sh = b_.w2_bf16;
+      ss.s[0].sh_t = b_.w2t_bf16;
+    }
     ss.s[0].t_co = C2; ss.s[0].t_taps = 9; ss.s[0].t_ci = C1;
     opt(ss.s[1], b_.off_b2);
     opt(ss.s[2], b_.off_w1);
     opt(ss.s[3], b_.off_b1);
-    ss.count = 4;
     ss.sgd = sa;
-    if (!fc_role) {
+    if (!pl.fc_role) {
       // fc bias: its gradient (fc_bwd block 0) is already final; a 1-row "slab" in place
       // (level-3 fc role: its last block applies it - that role runs inside this launch)
       ss.s[4] = SlabSeg{G + b_.off_bfc, (long)NO, 0, (long)NO, 1, G + b_.off_bfc, 1.f};
@@ -422,66 +359,192 @@ void SimpleCNNEngine::launch_step(int B, int stride, bool first_momentum_step, u
       ss.step_ctr = b_.step_ctr;  // the step's last kernel advances the batch window
     }
   }
-  ss.sys_store = use_x ? 1 : 0;  // bucket 1 likewise
+  ss.sys_store = pl.use_x ? 1 : 0;  // bucket 1 is read by the peers over xGMI
+  return ss;
+}
+
+bool SimpleCNNEngine::launch_step_head(int B, const SgdArgs& sa, const ShadowSet& sh, const C1Src& c1,
+                                       const FwdDz& dzo) {
+  // the previous step's pair (its fused SGD writes this step's parameters write-through)
+  // + this step's forward; two launches (same bits) when the merged grid does not fit.
+  // The head's fused SGD refreshes the shadows its forward reads (conv2 bf16, fc fragment
+  // order); the conv2 [tap][ci][co] copy (the next backward's) is written after the conv
+  // bucket's count (FwdMerge late).  The same bytes as sh, in two passes.
+  // Only when the whole conv2 weight lies in the one-shot conv-stage bucket: its blocks
+  // then rewrite exactly the quads they updated (no wait on another block); any other plan
+  // refreshes every shadow in the SGD pass as before.
+  ShadowSet sh_head = sh, late{};
+  if (late_shadow_ok(b_.off_w2, (long)cfg_.C2 * 9 * cfg_.C1)) {
+    sh_head.r[1] = sh.r[2];
+    sh_head.count = 2;
+    late.r[0] = sh.r[1];
+    late.count = 1;
+  }
+  BwdXar hx;
+  int* mc = b_.sync_flags + L3_HEAD_OFF;
+  bool head_used = false;
+  if (cfg_.pxt_fwd == 1 && B == cfg_.max_batch) {
+    if (!make_xar(hx, sa, b_.momentum, sh_head)) throw std::runtime_error("engine: the step head needs the pair plan");
+    hx.step_ctr = nullptr;  // (advanced by the fc role)
+    head_used = conv3x3_step_head(hx, mc, mc + FWD_DZ_CNT_STRIDE, b_.w2_bf16, b_.params + b_.off_b2, b_.a2, B,
+                                  b_.wfc_frag, b_.fc_part, c1, dzo, b_.sync_err, cs_, &late);
+  }
+  if (!head_used) {
+    if (!make_xar(hx, sa, b_.momentum, sh)) throw std::runtime_error("engine: the step head needs the pair plan");
+    hx.step_ctr = nullptr;
+    xgmi_allreduce_pair(hx, cs_);
+  }
+  DDP_HIP_CHECK(hipGetLastError());
+  return head_used;
+}
+
+// One training step: forward -> fc backward set-up -> slab set -> conv backward + bucket
+// all-reduces -> optimizer, on the chain plan(B) names.  T = float is the exact-fp32 step:
+// the same launchers on fp32 operands (StepOperands), from level 1 up, always whole.
+template <typename T>
+void SimpleCNNEngine::launch_step_t(int B, int stride, bool first_momentum_step, unsigned parts) {
+  constexpr bool BF16 = std::is_same<T, bf16_t>::value;  // level 0 and the step head: bf16 only
+  if (!BF16 && parts != PART_ALL) throw std::runtime_error("engine: the fp32 step runs whole (no step-head merge)");
+  const int H = cfg_.H, W = cfg_.W, HW = H * W, C1 = cfg_.C1, C2 = cfg_.C2, NO = cfg_.NO;
+  if (B <= 0 || B > cfg_.max_batch) throw std::runtime_error("engine: bad batch size");
+  const StepPlan pl = plan(B);
+  if ((parts & (PART_HEAD | PART_AR)) && !pl.ov && parts != PART_ALL)
+    throw std::runtime_error("engine: a split step needs the dist_mode 4 chain");
+  if (BF16 && !pl.l3 && plain_stale_) {
+    // the plain bf16 fc shadow (read by the level-1 fc backward) was not refreshed by the
+    // level-3 steps before this one: re-derive every shadow from the fp32 master first
+    // (the fp32 level-1 fc backward reads the master itself)
+    refresh_shadows();
+    plain_stale_ = false;
+  }
+  const StepOperands<T> op = step_operands<T>(b_, shadow_set(!pl.l3));
+  float* P = b_.params;
+  float* G = b_.grads;
+  float* M = b_.momentum;  // null when momentum == 0
+  const float inv_ws = 1.f / (float)cfg_.world;
+  const SgdArgs sa{cfg_.lr, cfg_.momentum, cfg_.dampening, cfg_.weight_decay, cfg_.nesterov,
+                   cfg_.maximize, first_momentum_step ? 1 : 0, 1};
+
+  // ---- forward (PART_HEAD: in one launch with the previous step's bucket all-reduces)
+  const C1Src c1 = make_c1src(B, stride, pl);
+  const FwdDz dzo = pl.l3 ? make_fwd_dz(B) : FwdDz{};
+  bool head_used = false;
+  if constexpr (BF16) {
+    if (parts & PART_HEAD) {
+      if (first_momentum_step) throw std::runtime_error("engine: the step head runs the steady-state SGD only");
+      head_used = launch_step_head(B, sa, op.sh, c1, dzo);
+    }
+  }
+  if ((parts & PART_FWD) || ((parts & PART_HEAD) && !head_used)) {
+    if constexpr (BF16) {
+      if (!pl.f1) conv1_fwd(b_.images, true, c1.bi, P + b_.off_w1, P + b_.off_b1, b_.a1, B, H, W, C1, cs_);
+    }
+    conv3x3_fwd(pl.f1 ? nullptr : op.a1, op.w2, P + b_.off_b2, op.a2, B, H, W, C1, C2, true, op.wfc_frag,
+                b_.fc_part, NO, cfg_.pxt_fwd, cs_, pl.f1 ? &c1 : nullptr, pl.l3 ? &dzo : nullptr);
+  }
+  if (parts & (PART_FWD | PART_HEAD)) last_head_ = head_used;
+  if (head_used && capturing_) graph_heads_ += 1;
+  if (!(parts & (PART_BWD | PART_AR))) return;
+
+  // ---- loss + fc backward set-up (bucket 0).  Level 3, single process or a one-stream xGMI
+  // chain: the fc weight gradient runs as a third role of the conv backward launch (BwdFc);
+  // otherwise as its own kernel before it - level 3: light, no dZ2 and no cross-entropy
+  // prologue (the forward wrote dZ2, dL and the losses); level 1: with both
+  if constexpr (BF16) {
+    if (!pl.f1)
+      xent_rows(b_.fc_part, HW, 64 * cfg_.pxt_fwd, P + b_.off_bfc, NO, B, b_.labels, c1.bi, b_.dlogits,
+                b_.loss_rows, 1.f / (float)B, cs_);
+  }
+  const FcBwdExtras ex = make_fc_extras(B, pl, sa);
+  float* dWfc = pl.fopt ? nullptr : G + b_.off_wfc;
+  const long K = (long)HW * C2;
+  BwdFc fcr;
+  std::function<void(hipStream_t)> fc_launch;  // the fc weight-gradient kernel, when not a role
+  if (pl.fc_role) {
+    fcr.a2 = op.a2;
+    fcr.dl = b_.dlogits;
+    fcr.dW = dWfc;
+    fcr.scale = inv_ws;
+    fcr.K = K;
+    fcr.ex = ex;
+  } else {
+    fc_launch = [&](hipStream_t s) {
+      fc_bwd(b_.dlogits, op.a2, pl.l3 ? nullptr : op.wfc, pl.l3 ? nullptr : op.dz2, dWfc, inv_ws, B, K, NO,
+             /*mask=*/true, s, ex);
+    };
+  }
+  if (BF16 && pl.l3) plain_stale_ = true;
+
+  // ---- slab set
+  const SlabSet ss = make_slabs(B, pl, sa);
+
+  // ---- conv backward (bucket 1) + the slab reduction + the bucket all-reduces
+  C1Src c1b;  // the compact batch the forward wrote, read with the identity index
+  c1b.x = b_.xb;
+  c1b.bi = BatchIdx{nullptr, nullptr, 0, 0};
+  c1b.bi.n_rows = B;
+  c1b.w = c1.w;
+  c1b.b = c1.b;
   bool reduced = false;  // the conv backward launch also did grad_reduce's work
   BwdXar xa;
-  const bool want_xar = xar_mode && cfg_.dist_mode == 2 && fc_role && fred && make_xar(xa, sa, M, sh_all);
-  if (dist && use_x && l3 && cfg_.dist_mode == 2 && !want_xar && std::getenv("DDP_AMD_XAR_DEBUG"))
+  const bool want_xar = pl.xar_wanted && make_xar(xa, sa, M, op.sh);
+  if (pl.use_x && pl.l3 && cfg_.dist_mode == 2 && !want_xar && std::getenv("DDP_AMD_XAR_DEBUG"))
     fprintf(stderr, "[ddp_amd] in-launch all-reduce off: plan_ok %d fc_role %d fred %d buckets %d\n",
-            (int)xar_plan_ok_, (int)fc_role, (int)fred, (int)buckets_.size());
+            (int)xar_plan_ok_, (int)pl.fc_role, (int)pl.fred, (int)buckets_.size());
   bool xar_used = false, pair_used = false;
   auto conv_launch = [&]() {
     if (!(parts & PART_BWD)) {  // (dist_mode 4: the last step's pair alone)
-    } else if (f1) {
+    } else if (pl.f1) {
       // dZ1 only feeds conv1's weight gradient, which the dgrad role computes in registers
-      reduced = conv3x3_bwd(b_.dz2, b_.w2t_bf16, nullptr, b_.w1slab, b_.w2slab, B, H, W, C1, C2, cfg_.pxt_dgrad,
-                            cfg_.wgrad_rows, c1b, cfg_.store_a1 ? b_.a1 : nullptr, cfg_.store_a1 == 2, cs_,
-                            fred ? &ss : nullptr, b_.sync_flags, b_.sync_err, cfg_.wgrad_split,
-                            fc_role ? &fcr : nullptr, !dist && cfg_.fuse_reduce == 2, want_xar ? &xa : nullptr,
-                            &xar_used);
-    } else {
-      conv3x3_dgrad(b_.dz2, nullptr, b_.w2t_bf16, b_.a1, b_.dz1, B, H, W, C1, C2, b_.images, true, bi,
+      reduced = conv3x3_bwd(op.dz2, op.w2t, nullptr, b_.w1slab, b_.w2slab, B, H, W, C1, C2, cfg_.pxt_dgrad,
+                            cfg_.wgrad_rows, c1b, cfg_.store_a1 ? op.a1 : nullptr, cfg_.store_a1 == 2, cs_,
+                            pl.fred ? &ss : nullptr, b_.sync_flags, b_.sync_err, cfg_.wgrad_split,
+                            pl.fc_role ? &fcr : nullptr, !pl.dist && cfg_.fuse_reduce == 2,
+                            want_xar ? &xa : nullptr, &xar_used);
+    } else if constexpr (BF16) {
+      conv3x3_dgrad(b_.dz2, nullptr, b_.w2t_bf16, b_.a1, b_.dz1, B, H, W, C1, C2, b_.images, true, c1.bi,
                     b_.w1slab, cfg_.pxt_dgrad, cs_, nullptr);
       conv3x3_wgrad(b_.dz2, nullptr, b_.a1, b_.w2slab, B, H, W, C1, C2, cfg_.wgrad_rows, cs_, nullptr);
     }
     if (!reduced && (parts & PART_BWD)) grad_reduce(ss, cs_);
-    if (one_stream && !xar_used && (parts & PART_AR)) {
+    if (pl.one_stream && !xar_used && (parts & PART_AR)) {
       // dist_mode 3 / 4 (or the in-launch all-reduce did not apply): the bucket all-reduces
       // behind the conv backward on the compute stream - both in one launch when the plan allows
       BwdXar pr;
-      if (cfg_.dist_mode >= 3 && make_xar(pr, sa, M, sh_all)) {
-        if (ov) pr.step_ctr = nullptr;  // (advanced by the fc role)
+      if (cfg_.dist_mode >= 3 && make_xar(pr, sa, M, op.sh)) {
+        if (pl.ov) pr.step_ctr = nullptr;  // (advanced by the fc role)
         xgmi_allreduce_pair(pr, cs_);
         pair_used = true;
         DDP_HIP_CHECK(hipGetLastError());
       } else {
-        enqueue_buckets(0, use_x, cs_, sa, M, sh_all);
-        enqueue_buckets(1, use_x, cs_, sa, M, sh_all);
+        enqueue_buckets(0, pl.use_x, cs_, sa, M, op.sh);
+        enqueue_buckets(1, pl.use_x, cs_, sa, M, op.sh);
       }
     }
   };
   // fc buckets overlap the conv backward: in-launch (dist_mode 2), or the fc weight gradient
   // forks off the compute stream after the forward (dist_mode 1); the one-stream chains run
   // the fc weight-gradient kernel (when it is not a role of the conv backward) first
-  if (one_stream) {
+  if (pl.one_stream) {
     if (fc_launch && (parts & PART_BWD)) fc_launch(cs_);
     conv_launch();
   } else {
-    schedule_backward(dist, dist && l3 && cfg_.dist_mode == 1, use_x, fc_launch, conv_launch, sa, M, sh_all);
+    schedule_backward(pl.dist, pl.fork, pl.use_x, fc_launch, conv_launch, sa, M, op.sh);
   }
   if (!(parts & PART_BWD)) {  // (a lone pair: the step's other flags stay those of its backward)
     last_pair_ = pair_used;
     return;
   }
   last_fused_reduce_ = reduced;
-  last_level3_ = l3;
-  last_fc_role_ = fc_role;
+  last_level3_ = pl.l3;
+  last_fc_role_ = pl.fc_role;
   last_xar_ = xar_used;
   last_pair_ = pair_used || head_used;
-  if (fopt) return;
-  if (dist && use_x) return;  // the optimizer ran inside the all-reduces
-  // ---- optimizer + bf16 shadows + next batch window
-  sgd_step(P, G, M, b_.n_params, sa, sh_all, b_.step_ctr, cs_);
+
+  // ---- optimizer + shadows + next batch window, unless an epilogue (fopt) or the xGMI
+  // all-reduces already ran it
+  if (pl.fopt || pl.use_x) return;
+  sgd_step(P, G, M, b_.n_params, sa, op.sh, b_.step_ctr, cs_);
 }
 
 void SimpleCNNEngine::launch_buckets(int stage, bool use_x, const SgdArgs& sa, float* M, const ShadowSet& sh) {
@@ -626,203 +689,6 @@ void SimpleCNNEngine::schedule_backward(bool dist, bool fork, bool use_x, const 
 void SimpleCNNEngine::join_buckets() {
   // the comm stream is in order: its last recorded event covers every earlier bucket
   DDP_HIP_CHECK(hipStreamWaitEvent(cs_, stage_used_[1] ? e_d1_ : e_d0_, 0));
-}
-
-// The exact-fp32 step: the bf16 chains on fp32 operands.  Level 3 (default): the forward
-// also computes dL and dZ2 (per-image in-launch granule sweep), and one conv backward launch runs the
-// dgrad and wgrad roles (both split over input-channel halves at two blocks per CU:
-// wgrad_split 2), the fc weight gradient + SGD as a third role (single process) and the
-// fused slab reduction + SGD.  Level 1: forward -> fc backward (cross-entropy prologue) ->
-// conv backward (+ the slab reduction).  Both chains give the same bits.
-void SimpleCNNEngine::launch_step_f32(int B, int stride, bool first_momentum_step) {
-  const int H = cfg_.H, W = cfg_.W, HW = H * W, C1 = cfg_.C1, C2 = cfg_.C2, NO = cfg_.NO;
-  if (B <= 0 || B > cfg_.max_batch) throw std::runtime_error("engine: bad batch size");
-  const bool use_x = xgmi_ && (xgmi_->world() > 1 || cfg_.force_allreduce);
-  const bool dist = use_x || (comm_ && (comm_->world() > 1 || cfg_.force_allreduce));
-  const float inv_ws = 1.f / (float)cfg_.world;
-  BatchIdx bi{b_.idx, b_.step_ctr, stride, 0};
-  bi.n_idx = b_.n_idx;
-  bi.n_rows = b_.n_rows;
-  float* P = b_.params;
-  float* G = b_.grads;
-  float* M = b_.momentum;
-  C1Src c1;
-  c1.x = b_.images;
-  c1.bi = bi;
-  c1.w = P + b_.off_w1;
-  c1.b = P + b_.off_b1;
-  c1.xb_out = b_.xb;
-  c1.yb_out = b_.yb;
-  c1.labels = b_.labels;
-  BatchIdx bid{nullptr, nullptr, 0, 0};
-  bid.n_rows = B;
-  C1Src c1b;
-  c1b.x = b_.xb;
-  c1b.bi = bid;
-  c1b.w = c1.w;
-  c1b.b = c1.b;
-  const bool l3 = level3_active(B);
-  const bool fred = cfg_.fuse_reduce && b_.sync_flags;  // grad_reduce inside the conv bwd
-  const bool pair_mode = dist && use_x && cfg_.dist_mode >= 3 && sync_ok_for_xar();  // (see launch_step)
-  if (fred || l3 || pair_mode) {  // the forward resets the step's hand-off counters
-    const int nfwd = conv3x3_dgrad_blocks(B, H, W, cfg_.pxt_fwd);
-    const int nsync = SYNC_RED_INTS + ((l3 || pair_mode) ? L3_FC_INTS : 0);
-    c1.zero_i32 = b_.sync_flags;
-    c1.zero_per_block = (nsync + nfwd - 1) / nfwd;
-    c1.zero_total = nsync;
-  }
-  const long n_w2 = (long)C2 * 9 * C1, w2row = n_w2 + C2, n_fc = (long)NO * HW * C2;
-  const SgdArgs sa{cfg_.lr, cfg_.momentum, cfg_.dampening, cfg_.weight_decay, cfg_.nesterov,
-                   cfg_.maximize, first_momentum_step ? 1 : 0, 1};
-  const bool fopt = !dist && cfg_.fuse_opt;
-  FwdDz dzo;
-  if (l3) {
-    dzo.dz2_f32 = b_.dz2_f32;
-    dzo.gran = gran_;
-    dzo.gen = gen_;
-    dzo.fc_bias = P + b_.off_bfc;
-    dzo.gscale = 1.f / (float)B;
-    dzo.err = b_.sync_err;
-    dzo.dl_out = b_.dlogits;
-    dzo.loss_rows = b_.loss_rows;
-  }
-  const bool xar_mode = dist && use_x && l3 &&
-                        ((cfg_.dist_mode == 2 && xar_plan_ok_) || cfg_.dist_mode >= 3);
-  const bool one_stream = xar_mode || pair_mode;  // (fp32: dist_mode 4 runs mode 3's chain)
-  const bool fc_role = l3 && (!dist || xar_mode) && cfg_.l3_fc_role &&
-                       conv3x3_bwd_fc_role_ok(H, W, C1, C2, cfg_.pxt_dgrad, cfg_.wgrad_split);
-
-  // ---- forward: conv1 (recomputed) + conv2 + bias + ReLU -> a2, fused fc partial logits
-  //      (level 3: then dL and dZ2 after the per-image granule sweep)
-  conv3x3_fwd(static_cast<const float*>(nullptr), P + b_.off_w2, P + b_.off_b2, b_.a2_f32, B, H, W, C1, C2,
-              true, b_.wfc_frag32, b_.fc_part, NO, cfg_.pxt_fwd, cs_, &c1, l3 ? &dzo : nullptr);
-  // ---- loss + fc backward (bucket 0)
-  FcBwdExtras ex;
-  ex.dbias = G + b_.off_bfc;
-  ex.dbias_scale = inv_ws;
-  ex.loss_out = b_.loss_hist;
-  ex.step_ctr = b_.step_ctr;
-  ex.sys_store = use_x ? 1 : 0;
-  if (l3) {
-    ex.loss_rows = b_.loss_rows;  // dL and the row losses come from the forward
-    ex.gen_inc = gen_;            // the next forward's granule tags: a new generation
-  } else {
-    ex.part = b_.fc_part;
-    ex.HW = HW;
-    ex.CH = 64 * cfg_.pxt_fwd;
-    ex.fc_bias = P + b_.off_bfc;
-    ex.labels32 = b_.yb;
-    ex.bi = bid;
-    ex.gscale = 1.f / (float)B;
-  }
-  if (fopt) {  // each block / wave updates only the fc columns it alone reads: race free in place
-    ex.sgd = sa;
-    ex.p_w = P + b_.off_wfc;
-    ex.m_w = M ? M + b_.off_wfc : nullptr;
-    ex.sh_frag32 = b_.wfc_frag32;  // the forward's fc operand
-    ex.frag_HW = HW;
-    ex.frag_C = C2;
-  }
-  BwdFc fcr;
-  std::function<void(hipStream_t)> fc_launch;  // the fc weight-gradient kernel, when not a role
-  if (fc_role) {
-    // inside the conv backward launch: block 0 of the fc role owns the fc bias, the loss and
-    // the step counter (nothing else in the launch reads them)
-    if (fopt) {
-      ex.p_b = P + b_.off_bfc;
-      ex.m_b = M ? M + b_.off_bfc : nullptr;
-      ex.step_inc = b_.step_ctr;
-    }
-    fcr.a2 = b_.a2_f32;
-    fcr.dl = b_.dlogits;
-    fcr.dW = fopt ? nullptr : G + b_.off_wfc;
-    fcr.scale = inv_ws;
-    fcr.K = (long)HW * C2;
-    fcr.ex = ex;
-  } else if (l3) {
-    fc_launch = [&](hipStream_t s) {
-      fc_bwd(b_.dlogits, b_.a2_f32, nullptr, nullptr, fopt ? nullptr : G + b_.off_wfc, inv_ws, B, (long)HW * C2,
-             NO, /*mask=*/true, s, ex);
-    };
-  } else {
-    fc_launch = [&](hipStream_t s) {
-      fc_bwd(b_.dlogits, b_.a2_f32, P + b_.off_wfc, b_.dz2_f32, fopt ? nullptr : G + b_.off_wfc, inv_ws, B,
-             (long)HW * C2, NO, /*mask=*/true, s, ex);
-    };
-  }
-  ShadowSet sh1{};
-  sh1.r[0] = ShadowRegion{b_.off_w2, n_w2, nullptr, SHADOW_F32_TAPT, C2, 9, C1, b_.w2t_f32};
-  sh1.r[1] = ShadowRegion{b_.off_wfc, n_fc, nullptr, SHADOW_F32_FCFRAG, HW, C2, 0, b_.wfc_frag32};
-  sh1.count = 2;
-  // ---- conv backward (bucket 1) + the slab reduction (fused into it, or grad_reduce)
-  SlabSet ss{};
-  const int wblk = conv3x3_wgrad_blocks(B, H, cfg_.wgrad_rows);
-  ss.s[0] = SlabSeg{b_.w2slab, w2row, 0, n_w2, wblk, G + b_.off_w2, inv_ws};
-  ss.s[1] = SlabSeg{b_.w2slab, w2row, n_w2, (long)C2, wblk, G + b_.off_b2, inv_ws};
-  const int dblk = conv3x3_dgrad_blocks(B, H, W, cfg_.pxt_dgrad);
-  ss.s[2] = SlabSeg{b_.w1slab, 320, 0, (long)C1 * 9, dblk, G + b_.off_w1, inv_ws};
-  ss.s[3] = SlabSeg{b_.w1slab, 320, (long)C1 * 9, (long)C1, dblk, G + b_.off_b1, inv_ws};
-  ss.count = 4;
-  if (fopt) {
-    auto opt = [&](SlabSeg& sg, long off) {
-      sg.p = P + off;
-      sg.m = M ? M + off : nullptr;
-    };
-    opt(ss.s[0], b_.off_w2);
-    ss.s[0].sh_t32 = b_.w2t_f32;
-    ss.s[0].t_co = C2; ss.s[0].t_taps = 9; ss.s[0].t_ci = C1;
-    opt(ss.s[1], b_.off_b2);
-    opt(ss.s[2], b_.off_w1);
-    opt(ss.s[3], b_.off_b1);
-    if (!fc_role) {
-      // fc bias: its gradient (fc_bwd block 0) is already final; a 1-row "slab" in place
-      ss.s[4] = SlabSeg{G + b_.off_bfc, (long)NO, 0, (long)NO, 1, G + b_.off_bfc, 1.f};
-      opt(ss.s[4], b_.off_bfc);
-      ss.count = 5;
-      ss.step_ctr = b_.step_ctr;
-    }
-    ss.sgd = sa;
-  }
-  ss.sys_store = use_x ? 1 : 0;
-  bool reduced = false;
-  BwdXar xa;
-  const bool want_xar = xar_mode && cfg_.dist_mode == 2 && fc_role && fred && make_xar(xa, sa, M, sh1);
-  bool xar_used = false, pair_used = false;
-  auto conv_launch = [&]() {
-    reduced = conv3x3_bwd(b_.dz2_f32, b_.w2t_f32, nullptr, b_.w1slab, b_.w2slab, B, H, W, C1, C2, cfg_.pxt_dgrad,
-                          cfg_.wgrad_rows, c1b, static_cast<const float*>(nullptr), false, cs_,
-                          fred ? &ss : nullptr, b_.sync_flags, b_.sync_err, cfg_.wgrad_split,
-                          fc_role ? &fcr : nullptr, !dist && cfg_.fuse_reduce == 2, want_xar ? &xa : nullptr,
-                          &xar_used);
-    if (!reduced) grad_reduce(ss, cs_);
-    if (one_stream && !xar_used) {
-      // dist_mode 3 (or the in-launch all-reduce did not apply): the bucket all-reduces behind
-      // the conv backward on the compute stream - both in one launch when the plan allows
-      BwdXar pr;
-      if (cfg_.dist_mode >= 3 && make_xar(pr, sa, M, sh1)) {
-        xgmi_allreduce_pair(pr, cs_);
-        pair_used = true;
-        DDP_HIP_CHECK(hipGetLastError());
-      } else {
-        enqueue_buckets(0, use_x, cs_, sa, M, sh1);
-        enqueue_buckets(1, use_x, cs_, sa, M, sh1);
-      }
-    }
-  };
-  if (one_stream) {
-    if (fc_launch) fc_launch(cs_);
-    conv_launch();
-  } else {
-    schedule_backward(dist, dist && l3 && cfg_.dist_mode == 1, use_x, fc_launch, conv_launch, sa, M, sh1);
-  }
-  last_fused_reduce_ = reduced;
-  last_level3_ = l3;
-  last_fc_role_ = fc_role;
-  last_xar_ = xar_used;
-  last_pair_ = pair_used;
-  if (fopt) return;
-  if (dist && use_x) return;
-  sgd_step(P, G, M, b_.n_params, sa, sh1, b_.step_ctr, cs_);
 }
 
 void SimpleCNNEngine::set_xgmi(std::shared_ptr<XgmiComm> x, std::vector<int> channels) {

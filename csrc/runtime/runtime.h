@@ -13,6 +13,7 @@
 
 #include "kernels/launchers.h"
 #include "runtime/bucket_state.h"
+#include "runtime/step_plan.h"
 
 #define DDP_HIP_CHECK(expr)                                                              \
   do {                                                                                   \
@@ -202,12 +203,15 @@ struct EngineBuffers {
   int* step_ctr;
   unsigned char* xb;  // the step's batch, compact: u8 [max_batch][H*W] (fuse level 1)
   int* yb;            // its labels [max_batch]
-  // in-launch hand-offs, zeroed by each step's forward (C1Src::zero_i32): [0, 256) the
-  // fused conv backward's 8 arrival counters (32 ints apart), [256, 256 + fc blocks) the
-  // level-2 dZ2 flags; level 3: [256] the fc backward's last-block counter (zeroed by the
-  // forward too) and, dist_mode 4, [L3_HEAD_OFF, + 2 * FWD_DZ_CNT_STRIDE) the step head's two
-  // bucket-done counters (zeroed by the fc backward's last block); sync_err: wait-timeout
-  // word (0 = ok, 1 = dZ2 wait, 2 = reduction, 3 = level-3 forward's granule sweep)
+  // in-launch hand-offs: [0, SYNC_RED_INTS) the fused conv backward's 8 arrival counters
+  // (32 ints apart); level 3 and the one-stream xGMI chains: [SYNC_RED_INTS, + L3_FC_INTS)
+  // the fc backward's last-block counter and, 8 / 16 / 24 ints in, the bucket all-reduce
+  // roles' fc_done / red_done / xar_done counters (make_xar) - all of these zeroed by each
+  // step's forward (C1Src::zero_i32); dist_mode 4: [L3_HEAD_OFF, + 2 * FWD_DZ_CNT_STRIDE) the
+  // step head's two bucket-done counters (zeroed by the fc backward's last block).
+  // sync_err: the wait-timeout word, sticky (0 = ok, RED_ERR = fused slab reduction,
+  // FWD_DZ_ERR = level-3 forward's granule sweep, XAR_ERR = in-launch all-reduce,
+  // HEAD_ERR = step head; launchers.h)
   int* sync_flags = nullptr;
   int* sync_err = nullptr;
   // data
@@ -219,76 +223,6 @@ struct EngineBuffers {
 
 constexpr int L3_FC_INTS = 32;                          // [SYNC_RED_INTS, + 32): fc last-block counter
 constexpr int L3_HEAD_OFF = SYNC_RED_INTS + L3_FC_INTS;  // dist_mode 4: the two bucket-done counters
-
-struct EngineConfig {
-  int max_batch, H, W, C1, C2, NO;
-  int pxt_fwd, pxt_dgrad, wgrad_rows;
-  int world, rank;
-  float lr, momentum, dampening, weight_decay;
-  int nesterov, maximize;
-  int force_allreduce;  // run the bucket all-reduces even at world size 1 (tests)
-  // 0: 8 kernels (a1 materialised, separate cross-entropy kernel)
-  // 1: 6 kernels - conv1 recomputed inside conv2 fwd/dgrad/wgrad from the uint8
-  //    images (a1 never touches HBM) and cross-entropy folded into fc_bwd
-  //    (4 per step with the fused optimizer: conv fwd, fc_bwd, conv bwd, grad_reduce)
-  // (2: a level-1 variant with fc_bwd and the conv backward in one launch - measured
-  //    slower than level 1 and removed in round 4)
-  // 3: the fc backward leaves the critical path - the conv forward computes dZ2 itself
-  //    (FwdDz: per-image in-launch granule sweep, then dL and dZ2 from the fc weight fragments it
-  //    holds) and the fc weight gradient + fused SGD (fc_bwd without dX, dL given) runs as
-  //    a third role of the conv backward launch (single process, l3_fc_role: 2 kernels per
-  //    step), or as a light kernel between the two (world size > 1: the fc bucket's
-  //    all-reduce overlaps the conv backward).  bf16, where every forward block fits on the
-  //    GPU at once (conv3x3_fwd_dz_fits); otherwise the level-1 chain
-  int fuse_level = 0;
-  // level 3, single process: 1 = the fc weight gradient as a role of the conv backward
-  // launch, on blocks after every conv block (the resident slots they leave free); 0 = as
-  // its own kernel (what world size > 1 runs).  (Placements 2 / 3 - right after the dgrad
-  // blocks, on the dgrad blocks - measured slower and were removed in round 4.)
-  int l3_fc_role = 1;
-  // 1: single-process steps apply SGD in the epilogues of fc_bwd / grad_reduce (no
-  //    separate optimizer kernel); 0: always the flat SGD kernel (equivalence tests)
-  int fuse_opt = 1;
-  // level 1: 0 = the conv backward recomputes conv1 from the compact batch; 1 = the
-  // forward also stores a1 (own pixels) and the dgrad role reads its ReLU mask from it;
-  // 2 = the wgrad role reads a1 tiles too
-  int store_a1 = 0;
-  // 1: exact fp32 operands everywhere (v_mfma_f32_16x16x4_f32 conv2, fp32 fc, fp32
-  //    activations), the reference's precision; needs fuse_level 1 and store_a1 0
-  int f32 = 0;
-  // 1: the conv backward launch also reduces the split-K slabs + fused SGD (no separate
-  //    grad_reduce kernel; level >= 1, needs sync_flags) while its reducers fit half the
-  //    launch's resident capacity; 2: the whole capacity when the step has no bucket
-  //    all-reduce on another stream (single process: the exact-fp32 step fuses too);
-  //    0: grad_reduce kernel
-  int fuse_reduce = 1;
-  // 2: the fused conv backward's wgrad role runs two blocks per slab row, one per half of
-  //    conv2's input channels (bf16; bit-identical slabs); 1: one block per row
-  int wgrad_split = 1;
-  // world size > 1, level 3 - how the backward meets the bucket all-reduces:
-  //  2 = in-launch (xGMI, at most one bucket per stage): the fc weight gradient runs as the
-  //      conv backward's fc role, and role blocks at the head of that same launch all-reduce
-  //      each bucket (+ fused SGD) as soon as its gradients are final (BwdXar) - 2 kernels
-  //      per step, no cross-stream edge; falls back to the bucket kernels on the compute
-  //      stream when a condition fails (RCCL: mode 1)
-  //  1 = fork: fc_bwd and the fc buckets' all-reduces on the comm stream, forked after the
-  //      forward beside the conv backward (a graph branch), the conv buckets' all-reduces
-  //      behind the conv backward
-  //  3 = one stream (xGMI, the default): the fc role inside the conv backward as on one GPU,
-  //      then ONE launch running both buckets' all-reduces (+ fused SGD) side by side on
-  //      full grids (xgmi_allreduce_pair; the bucket kernels one by one when the plan has
-  //      more buckets per stage) - 3 kernels per step, no cross-stream edge.  Fastest
-  //      measured (forced world 1: 639k img/s vs 444k in-launch, 416k fork;
-  //      profiles/r5_dist/README.md): the in-launch roles get too few blocks, a graph
-  //      branch costs two cross-stream edges
-  //  0 = the round-4 order (fc_bwd in front of the conv backward, all-reduces on ms_)
-  //  4 = the step head (xGMI, bf16 level 3, pxt_fwd 1): mode 3's chain, but in a captured
-  //      graph the pair launch of step k also carries step k + 1's forward (conv3x3.hip
-  //      step_head_kernel: the forward blocks wait for each bucket's all-reduce blocks only
-  //      where they first read its parameters) - 2 launches per step instead of 3; the step
-  //      counter advances in the conv backward's fc role.  Same bits as mode 3.
-  int dist_mode = 3;
-};
 
 // Gradient bucket of the engine's data plane: a [off, off + n) range of the flat gradient
 // buffer.  Any plan works (DDP's bucket_cap_mb rule, sub-parameter chunks): a bucket is
@@ -314,14 +248,14 @@ class SimpleCNNEngine {
   int graph_steps() const { return graph_steps_; }
   void destroy_graph();
   hipStream_t stream() const { return cs_; }
-  void synchronize();  // throws if a level-2 hand-off wait timed out
-  // in-launch wait-timeout word (0 = ok, 1 = level-2 dZ2 wait, 2 = fused reduction,
-  // 3 = level-3 forward's granule sweep); sticky
+  void synchronize();  // throws if an in-launch hand-off wait of a step timed out (sync_error)
+  // in-launch wait-timeout word (EngineBuffers::sync_err: 0 = ok, RED_ERR, FWD_DZ_ERR,
+  // XAR_ERR or HEAD_ERR); sticky
   int sync_error() const { return err_host_ ? __atomic_load_n(err_host_, __ATOMIC_ACQUIRE) : 0; }
   // whether a step of `batch` images runs the level-3 chain (fuse_level 3 and it applies)
-  bool level3_active(int batch);
+  bool level3_active(int batch) { return plan(batch).l3; }
   // whether dist_mode 4's step head applies to a captured full-batch step
-  bool overlap_active();
+  bool overlap_active() { return plan(cfg_.max_batch).ov && pair_plan_ok_ && cfg_.pxt_fwd == 1; }
   // whether the last launched step reduced its weight-gradient slabs inside the conv
   // backward launch (false: separate grad_reduce kernel)
   bool last_fused_reduce() const { return last_fused_reduce_; }
@@ -350,7 +284,23 @@ class SimpleCNNEngine {
   // step's pair (step_head_kernel)
   enum : unsigned { PART_FWD = 1, PART_BWD = 2, PART_AR = 4, PART_HEAD = 8, PART_ALL = 7 };
   void launch_step(int batch, int batch_stride, bool first_momentum_step, unsigned parts = PART_ALL);
-  void launch_step_f32(int batch, int batch_stride, bool first_momentum_step);
+  // the step on bf16 operands (T = bf16_t) or on exact fp32 operands (T = float)
+  template <typename T>
+  void launch_step_t(int batch, int batch_stride, bool first_momentum_step, unsigned parts);
+  // the chain a step of `batch` images runs (step_plan.h: the only place that decides it)
+  StepPlan plan(int batch);
+  // every derived copy of the weights the step reads (a bucket's fused SGD refreshes the ones
+  // inside its range): bf16 - conv2 plain, conv2 [tap][ci][co], fc fragment order and, with
+  // plain_fc, the plain fc shadow; fp32 - the conv2 [tap][ci][co] and fc fragment-order copies
+  ShadowSet shadow_set(bool plain_fc) const;
+  // the blocks of a step, each filling one launcher struct (engine.cpp, in step order)
+  C1Src make_c1src(int B, int stride, const StepPlan& pl) const;
+  FwdDz make_fwd_dz(int B) const;
+  FcBwdExtras make_fc_extras(int B, const StepPlan& pl, const SgdArgs& sa) const;
+  SlabSet make_slabs(int B, const StepPlan& pl, const SgdArgs& sa) const;
+  // PART_HEAD (bf16): the previous step's pair + this step's forward in one launch; false:
+  // the merged grid does not fit - the pair ran alone and the caller launches the forward
+  bool launch_step_head(int B, const SgdArgs& sa, const ShadowSet& sh, const C1Src& c1, const FwdDz& dzo);
   // enqueue the all-reduces of the buckets of `stage` (0: after fc_bwd, 1: after
   // grad_reduce) on the comm stream behind an event of the compute stream; with xGMI the
   // optimizer (+ the shadows in `sh`) runs inside each bucket's all-gather and the last

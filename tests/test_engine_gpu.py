@@ -560,7 +560,8 @@ def test_comm_tune_rccl_candidates_world1():
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("plane,dtype", [("xgmi", "bf16"), ("xgmi", "fp32"), ("rccl", "bf16")])
+@pytest.mark.parametrize("plane,dtype", [("xgmi", "bf16"), ("xgmi", "fp32"), ("rccl", "bf16"),
+                                         ("rccl", "fp32")])
 def test_dist_chains_bitwise_world1(plane, dtype, monkeypatch):
     """every multi-GPU step chain trains to the same bits as the comm-free
     one-GPU chain, at world size 1 with the all-reduces forced and the 8-rank bucket plan (fc

@@ -2,8 +2,9 @@
 
 The reducer's bucket bookkeeping (csrc/runtime/bucket_state.h) has no device
 code, so it is compiled for the host with -fsanitize=address,undefined and run
-here (GPU sanitizers are not available on the MI355X pool).  The bound planner
-is also cross-checked against the Python bucket plan used by DDP.
+here (GPU sanitizers are not available on the MI355X pool); so is the fused
+step's chain selection (csrc/runtime/step_plan.h).  The bound planner is also
+cross-checked against the Python bucket plan used by DDP.
 """
 import os
 import shutil
@@ -14,13 +15,13 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.mark.skipif(shutil.which("g++") is None, reason="no host compiler")
-def test_bucket_state_asan_ubsan(tmp_path):
-    exe = tmp_path / "test_bucket_state"
+def _run_sanitized(tmp_path, name):
+    """Build tests/native/<name>.cpp (a stand-alone program) with ASan + UBSan and run it."""
+    exe = tmp_path / name
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer",
            "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
            "-I", os.path.join(ROOT, "csrc"),
-           os.path.join(ROOT, "tests", "native", "test_bucket_state.cpp"), "-o", str(exe)]
+           os.path.join(ROOT, "tests", "native", name + ".cpp"), "-o", str(exe)]
     subprocess.run(cmd, check=True, capture_output=True, timeout=300)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0")
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120, env=env)
@@ -28,6 +29,18 @@ def test_bucket_state_asan_ubsan(tmp_path):
         pytest.skip("another preloaded runtime precedes ASan in this environment")
     assert r.returncode == 0, r.stdout + r.stderr
     assert "all checks passed" in r.stdout
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no host compiler")
+def test_bucket_state_asan_ubsan(tmp_path):
+    _run_sanitized(tmp_path, "test_bucket_state")
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no host compiler")
+def test_step_plan_asan_ubsan(tmp_path):
+    """The fused step's chain selection (csrc/runtime/step_plan.h): the plans of the documented
+    configurations, and the invariants the engine relies on over every input combination."""
+    _run_sanitized(tmp_path, "test_step_plan")
 
 
 def test_native_planner_matches_python_bucket_plan():
