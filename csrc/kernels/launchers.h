@@ -376,6 +376,13 @@ struct SlabSet {
 void sgd_step(float* p, const float* g, float* mbuf, long n, const SgdArgs& a, const ShadowSet& sh,
               int* step_ctr, hipStream_t s, const float* gscale = nullptr, const float* lr_table = nullptr,
               int n_table = 0, SchedState* sched = nullptr);
+// One AdamW step over flat fp32 params / grads / first and second moments (adamw.hip), with
+// the same shadow refresh.  coef: n_coef entries of four floats {decay, step_size, bc2_sqrt, lr}
+// in device memory (16-byte aligned); the launch uses entry min(sched->t, n_coef - 1) and
+// advances sched->t (required: bias correction needs the step number).  gscale as sgd_step.
+void adamw_step(float* p, const float* g, float* mbuf, float* vbuf, long n, const AdamArgs& a,
+                const ShadowSet& sh, hipStream_t s, const float* gscale, const float* coef, int n_coef,
+                SchedState* sched);
 // ---- global gradient norm / clip coefficient (grad_norm.hip) --------------------------
 constexpr int GN_THREADS = 256, GN_QUADS = 4, GN_MAX_BLOCKS = 1024;
 struct ClipStats {

@@ -75,6 +75,15 @@ struct SchedState {
   float lr_used;
 };
 
+// torch.optim.AdamW constants of one step (adamw.hip): w1 = 1 - beta1, b2 = beta2,
+// w2 = 1 - beta2, each rounded once from float64.  What depends on the step number - the
+// decay, the bias corrections, the rate - is read from a device table indexed by SchedState::t.
+// update == 0: shadows only (no optimizer step: t does not advance)
+struct AdamArgs {
+  float w1, b2, w2, eps;
+  int maximize, update;
+};
+
 // diagnostic phase-stamp kernel ids / buffer geometry (common.h DDP_STAMP)
 enum { STAMP_K_CONV_FWD = 0, STAMP_K_FC_BWD = 1, STAMP_K_DGRAD = 2, STAMP_K_WGRAD = 3,
        STAMP_K_GRAD_REDUCE = 4, STAMP_K_SGD = 5, STAMP_K_XENT = 6, STAMP_K_CONV1 = 7,

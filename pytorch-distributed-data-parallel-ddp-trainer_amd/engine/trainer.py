@@ -32,7 +32,7 @@ from ..data import (DeviceImageLoader, DeviceImages, DeviceMNIST, DeviceMNISTLoa
                     load_mnist, synthetic_imagenet, synthetic_imagenet_test)
 from ..models import SimpleCNN, resnet18
 from ..models.layers import buffer_space, flat_space
-from ..ops import CrossEntropyLoss, FusedSGD
+from ..ops import CrossEntropyLoss, FusedAdamW, FusedSGD
 from ..parallel import DistributedDataParallel as DDP
 from ..parallel import cleanup, local_rank, native_comm, setup
 from ..utils.checkpoint import resume, save_checkpoint
@@ -85,6 +85,10 @@ class TrainOptions:
     lr_min: float = 0.0               # cosine / linear: the rate the decay ends at
     lr_step_epochs: int = 0           # step: multiply the rate by lr_gamma every N epochs
     lr_gamma: float = 0.1
+    optimizer: str = "sgd"            # sgd | adamw (adamw: module/CPU path)
+    beta1: float = 0.9                # adamw
+    beta2: float = 0.999              # adamw
+    adam_eps: float = 1e-8            # adamw
 
 
 def validate_options(opts: TrainOptions):
@@ -108,6 +112,10 @@ def validate_options(opts: TrainOptions):
         raise ValueError("--warmup_steps must be >= 0")
     if opts.lr_schedule == "step" and opts.lr_step_epochs < 1:
         raise ValueError("--lr_schedule step needs --lr_step_epochs N >= 1")
+    if opts.optimizer not in ("sgd", "adamw"):
+        raise ValueError(f"--optimizer must be sgd or adamw, got {opts.optimizer!r}")
+    if opts.optimizer == "adamw" and opts.momentum != 0:
+        raise ValueError("--momentum is SGD's; --optimizer adamw takes --beta1 / --beta2 / --adam_eps")
     if (opts.device or "").lower() == "gpu":  # the fused engine is certain: refuse before any process starts
         check_fused_engine_options(opts, opts.engine == "fused" and opts.model == "simplecnn")
 
@@ -125,6 +133,10 @@ def check_fused_engine_options(opts: TrainOptions, fused: bool):
         raise ValueError("--lr_schedule / --warmup_steps need the module path (--engine module) or the CPU "
                          "path; the fused engine bakes the learning rate into its kernels' arguments and "
                          "into its captured step graphs")
+    if fused and opts.optimizer != "sgd":
+        raise ValueError("--optimizer adamw needs the module path (--engine module) or the CPU path; the "
+                         "fused engine applies SGD inside the kernels that finish each gradient and keeps "
+                         "no second-moment state")
 
 
 def uses_lr_schedule(opts: TrainOptions) -> bool:
@@ -224,9 +236,14 @@ def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
     # the schedule is indexed by the global optimizer step: a table every rank builds alike from the
     # flags (no schedule object with the default flags: the by-value sgd_kernel runs)
     per_epoch = optimizer_steps_per_epoch(len(loader), opts.grad_accum, opts.max_steps)
-    opt = FusedSGD(model, lr=opts.lr, momentum=opts.momentum, weight_decay=opts.weight_decay,
-                   max_grad_norm=opts.clip_grad_norm or None,
-                   lr_schedule=build_lr_schedule(opts, epochs, per_epoch))
+    if opts.optimizer == "adamw":
+        opt = FusedAdamW(model, lr=opts.lr, betas=(opts.beta1, opts.beta2), eps=opts.adam_eps,
+                         weight_decay=opts.weight_decay, max_grad_norm=opts.clip_grad_norm or None,
+                         lr_schedule=build_lr_schedule(opts, epochs, per_epoch))
+    else:
+        opt = FusedSGD(model, lr=opts.lr, momentum=opts.momentum, weight_decay=opts.weight_decay,
+                       max_grad_norm=opts.clip_grad_norm or None,
+                       lr_schedule=build_lr_schedule(opts, epochs, per_epoch))
     model.train()
     print(f"Rank {rank}: Loss and Optimizer ready", flush=True)
 
@@ -236,7 +253,14 @@ def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
         print(f"Rank {rank}: No checkpoint found, starting from scratch.", flush=True)
     elif rank == 0:
         print(f"Rank {rank}: Resumed from {path}, starting at epoch {start_epoch}", flush=True)
-    if path is not None and opt.lr_schedule is not None:
+    if path is not None and opts.optimizer == "adamw":
+        # the Adam step is optimizer state: it came with the checkpoint, and is the schedule's index
+        if opt.schedule_step() != start_epoch * per_epoch:
+            print(f"Rank {rank}: WARNING: the checkpoint's optimizer step {opt.schedule_step()} is not "
+                  f"{start_epoch * per_epoch}, the step epoch {start_epoch} starts at in this run: the schedule "
+                  "flags, --epochs, --batch_size, --grad_accum, --max_steps and the world size must match "
+                  "the run that wrote the checkpoint", flush=True)
+    elif path is not None and opt.lr_schedule is not None:
         opt.set_schedule_step(start_epoch * per_epoch)  # the schedule is a function of the step index alone
         if opt.loaded_lr is not None and opt.loaded_lr != opt.current_lr():  # (rank 0: it read the file)
             print(f"Rank {rank}: WARNING: the checkpoint's lr {opt.loaded_lr!r} is not this schedule's rate "
@@ -391,13 +415,14 @@ def module_comm(comm: str) -> str:
 
 
 def replica_digest(fs, opt) -> str:
-    """SHA-1 of this rank's flat parameters (+ momentum): bitwise replica identity."""
+    """SHA-1 of this rank's flat parameters and every optimizer state buffer (SGD: momentum;
+    AdamW: both moments): bitwise replica identity."""
     import hashlib
 
     h = hashlib.sha1(fs.params.detach().cpu().numpy().tobytes())
-    mb = getattr(opt, "momentum_buffer", None)
-    if mb is not None:
-        h.update(mb.detach().cpu().numpy().tobytes())
+    for buf in opt.state_buffers().values():
+        if buf is not None:
+            h.update(buf.detach().cpu().numpy().tobytes())
     return h.hexdigest()
 
 

@@ -6,6 +6,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import reference
+from .adamw import FusedAdamW
 from .lr_schedule import LRSchedule
 from .sgd import FusedSGD
 
@@ -24,4 +25,4 @@ class CrossEntropyLoss(nn.Module):
         return F.cross_entropy(logits, labels)
 
 
-__all__ = ["CrossEntropyLoss", "FusedSGD", "LRSchedule", "reference"]
+__all__ = ["CrossEntropyLoss", "FusedAdamW", "FusedSGD", "LRSchedule", "reference"]

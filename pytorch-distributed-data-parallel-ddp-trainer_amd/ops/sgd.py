@@ -34,73 +34,40 @@ from __future__ import annotations
 
 import torch
 
-from ..models.layers import FlatSpace, flat_space
+from .flat_optim import FlatOptimizer, _from_reference_layout, _to_reference_layout
 
 _DEFAULTS = dict(lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False,
                  maximize=False, foreach=None, differentiable=False, fused=None)
 
 
-class FusedSGD:
+class FusedSGD(FlatOptimizer):
     def __init__(self, model: torch.nn.Module, lr: float = 1e-3, momentum: float = 0,
                  dampening: float = 0, weight_decay: float = 0, nesterov: bool = False,
                  maximize: bool = False, max_grad_norm: float | None = None, lr_schedule=None):
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
-        if max_grad_norm is not None and not float(max_grad_norm) > 0:
-            raise ValueError("max_grad_norm must be positive (None: no clipping)")
-        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
-        self._clip_ws = None      # GPU: (partials, ticket, stats), allocated by the first step
-        self._clip_host = None    # CPU: the same four numbers
-        self.lr_schedule = lr_schedule
-        self._sched_ws = None     # GPU: (table, state int32[4] = SchedState t / ticket / lr_used), first step
-        self._sched_t = 0         # CPU: the step index; GPU: the index the state block starts from
-        self.loaded_lr = None     # the lr of the last loaded state dict (with a schedule: not applied)
-        self.model = model
-        self.flat: FlatSpace = flat_space(model)
+        self._init_flat(model, max_grad_norm, lr_schedule)
         g = dict(_DEFAULTS)
         g.update(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
                  nesterov=nesterov, maximize=maximize)
         self.param_groups = [g]
-        self._reg_names = [n for n, _ in model.named_parameters()]
         self.momentum_buffer: torch.Tensor | None = None
-        self.shadows: list[tuple] = []  # (off, n, bf16 dst, kind, a, b, c)
-        self.steps = 0
 
     # ------------------------------------------------------------------ API
-    @property
-    def lr(self):
-        return self.param_groups[0]["lr"]
-
-    def zero_grad(self, set_to_none: bool = True):
-        # grads are views of the flat buffer: "none" is a memset that keeps the views - or no
-        # memset at all when every gradient's producer overwrites it (direct_grad lazy zeroing)
-        self.flat.zero_grad(lazy=True)
-
     @torch.no_grad()
     def step(self):
         g = self.param_groups[0]
         fs = self.flat
-        fs.reattach_grads()
-        from . import direct_grad
-
-        direct_grad.flush_fresh(p for p, _ in fs._pairs)
+        self._prepare_grads()
         first = self.momentum_buffer is None
         if g["momentum"] != 0 and first:
             self.momentum_buffer = torch.zeros_like(fs.params)
         if fs.params.is_cuda:
             from .. import native
 
-            shadows = self.shadows
-            if fs._bf16 is not None:  # the model's bf16 weight copy, refreshed in the same pass
-                shadows = shadows + [(0, fs.numel, fs._bf16, 1, 0, 0, 0)] + fs.pad4_shadows()
+            shadows = self._all_shadows()  # incl. the model's bf16 weight copy, refreshed in the same pass
             C = native.require()
-            gscale = None
-            if self.max_grad_norm is not None:
-                # the norm runs over the whole buffer: the alignment padding between
-                # parameters is zero and no producer writes it
-                partials, ticket, stats = self._clip_workspace(C)
-                C.grad_sqnorm(fs.grads, self.max_grad_norm, partials, ticket, stats)
-                gscale = stats[1:2]  # ClipStats::coef, read by the kernel at run time
+            gscale = self._gscale(C)
             # with a schedule every step, eager or captured, runs the DLR build: one device counter
             sched = self._sched_workspace() if self.lr_schedule is not None else None
             C.sgd(fs.params, fs.grads, self.momentum_buffer, g["lr"], g["momentum"],
@@ -111,77 +78,14 @@ class FusedSGD:
             self._step_torch(first)
         self.steps += 1
 
-    def _clip_workspace(self, C):
-        """Partials, the (zeroed) arrival ticket and the ClipStats words; allocated once, by
-        the first step - GraphedStep's warm-up, so before a capture."""
-        if self._clip_ws is None:
-            dev = self.flat.params.device
-            self._clip_ws = (torch.zeros(C.GRAD_NORM_MAX_BLOCKS, dtype=torch.float32, device=dev),
-                             torch.zeros(1, dtype=torch.int32, device=dev),
-                             torch.zeros(4, dtype=torch.float32, device=dev))
-        return self._clip_ws
+    def state_buffers(self) -> dict:
+        """The optimizer state as named flat tensors (``None``: not created yet) - what a
+        resume broadcasts and ``--verify_replicas`` hashes."""
+        return {"momentum_buffer": self.momentum_buffer}
 
-    def _sched_workspace(self):
-        """The float32 table and the SchedState words on the device; allocated once, by the
-        first step - GraphedStep's warm-up, so before a capture (as ``_clip_workspace``)."""
-        if self._sched_ws is None:
-            dev = self.flat.params.device
-            self._sched_ws = (self.lr_schedule.table.to(dev),
-                              torch.tensor([self._sched_t, 0, 0, 0], dtype=torch.int32).to(dev))
-        return self._sched_ws
-
-    def _need_schedule(self):
-        if self.lr_schedule is None:
-            raise RuntimeError("this FusedSGD has no lr_schedule")
-
-    def schedule_step(self) -> int:
-        """Optimizer steps the schedule has seen = the index of the next step's rate; on the
-        GPU one device-to-host read of the counter the kernel advances."""
-        self._need_schedule()
-        if self._sched_ws is not None:
-            return int(self._sched_ws[1][0].item())
-        return self._sched_t
-
-    def current_lr(self) -> float:
-        """The rate the next step will use (the constant ``lr`` without a schedule)."""
-        if self.lr_schedule is None:
-            return self.param_groups[0]["lr"]
-        return self.lr_schedule.lr_at(self.schedule_step())
-
-    def set_schedule_step(self, k: int):
-        """Continue the schedule at step ``k`` (resume).  On the GPU a host-to-device write of
-        the counter: never inside a graph capture."""
-        self._need_schedule()
-        k = int(k)
-        if k < 0:
-            raise ValueError("the schedule step must be >= 0")
-        self._sched_t = k
-        if self._sched_ws is not None:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("set_schedule_step inside a graph capture")
-            self._sched_ws[1].copy_(torch.tensor([k, 0, 0, 0], dtype=torch.int32))
-
-    def grad_clip_stats(self) -> dict | None:
-        """``{"total_norm", "coef", "steps", "clipped"}`` of the clipped steps so far (the norm
-        and coefficient are the last step's); one device-to-host read.  ``None`` without
-        ``max_grad_norm`` or before the first step."""
-        if self._clip_host is not None:
-            return dict(self._clip_host)
-        if self._clip_ws is None:
-            return None
-        s = self._clip_ws[2].cpu()
-        i = s.view(torch.int32)
-        return {"total_norm": s[0].item(), "coef": s[1].item(), "steps": int(i[2]), "clipped": int(i[3])}
-
-    def _clip_torch(self, d: torch.Tensor) -> torch.Tensor:
-        """The kernel's rule with torch ops: fp32 norm of the whole flat gradient (summed in
-        float64, rounded once), coef = min(1, max_norm / (norm + 1e-6)) in fp32, d * coef."""
-        norm = d.double().square().sum().sqrt().float()
-        coef = (torch.tensor(self.max_grad_norm, dtype=torch.float32) / (norm + 1e-6)).clamp(max=1.0)
-        h = self._clip_host or {"steps": 0, "clipped": 0}
-        self._clip_host = {"total_norm": norm.item(), "coef": coef.item(), "steps": h["steps"] + 1,
-                           "clipped": h["clipped"] + int(coef.item() < 1.0)}
-        return d * coef
+    def set_state_buffer(self, name: str, buf: torch.Tensor):
+        assert name == "momentum_buffer"
+        self.momentum_buffer = buf
 
     def _step_torch(self, first: bool):
         g = self.param_groups[0]
@@ -250,40 +154,3 @@ class FusedSGD:
         """A momentum buffer arrived from elsewhere (resume broadcast): treat as started."""
         if self.momentum_buffer is not None:
             self.steps = max(self.steps, 1)
-
-
-def _owner(model, name):
-    mod = model
-    for p in name.split(".")[:-1]:
-        mod = getattr(mod, p)
-    return mod, name.split(".")[-1]
-
-
-def _to_reference_layout(model, fs: FlatSpace, flat_buf: torch.Tensor) -> dict:
-    """Per-parameter tensors of ``flat_buf`` in the layout the reference state_dict uses."""
-    from ..models.layers import Conv2d, Linear
-
-    out = {}
-    for n in fs.names:
-        v = fs.view(flat_buf, n).detach()
-        mod, attr = _owner(model, n)
-        if attr == "weight" and isinstance(mod, Conv2d):
-            v = v.permute(0, 3, 1, 2)
-        elif attr == "weight" and isinstance(mod, Linear) and mod.in_layout is not None:
-            C, H, W = mod.in_layout
-            v = v.permute(0, 2, 1).reshape(mod.out_features, C * H * W)
-        out[n] = v.contiguous().clone()
-    return out
-
-
-def _from_reference_layout(model, fs: FlatSpace, ref: dict, flat_buf: torch.Tensor):
-    from ..models.layers import Conv2d, Linear
-
-    for n, v in ref.items():
-        mod, attr = _owner(model, n)
-        if attr == "weight" and isinstance(mod, Conv2d):
-            v = v.permute(0, 2, 3, 1)
-        elif attr == "weight" and isinstance(mod, Linear) and mod.in_layout is not None:
-            C, H, W = mod.in_layout
-            v = v.reshape(mod.out_features, C, H * W).permute(0, 2, 1)
-        fs.view(flat_buf, n).copy_(v)

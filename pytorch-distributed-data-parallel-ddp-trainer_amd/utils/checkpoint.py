@@ -12,8 +12,9 @@ zip record with the reference's own ``epoch_0.pt``).
 Fixes of the reference's resume path:
 * B6/B7/B8/B9 - the 33-broadcast per-key protocol (broken as shipped) is replaced
   by: rank 0 loads with ``weights_only=True``, then ONE broadcast of the epoch,
-  ONE broadcast of the flat parameter buffer (any dtype), ONE of the optimizer
-  state (momentum buffer) and the hyper-parameters;
+  ONE broadcast of the flat parameter buffer (any dtype), ONE per optimizer state
+  buffer (SGD: the momentum buffer; AdamW: both moments) and ONE of the
+  hyper-parameters (with AdamW's step counter);
 * B10 - the optimizer state is applied, not just read;
 * B11 - only ``*.pt`` files are candidates; newest by ``st_ctime`` with ties
   broken by the parsed epoch number (the reference picked by directory order);
@@ -134,16 +135,34 @@ def resume(model, optimizer, ckpt_dir="./checkpoints", rank: int = 0, world_size
             if bs is not None:
                 for t in bs.flat_list():
                     dist.broadcast(t, src=0)
-        hp = [optimizer.param_groups[0] if rank == 0 else None]
-        dist.broadcast_object_list(hp, src=0)
-        optimizer.param_groups[0].update(hp[0])
-        has_mom = torch.tensor([1 if getattr(optimizer, "momentum_buffer", None) is not None else 0],
-                               device=bdev)
-        dist.broadcast(has_mom, src=0)
-        if int(has_mom) == 1:
-            if optimizer.momentum_buffer is None:
-                optimizer.momentum_buffer = torch.zeros_like(flat.params)
-            dist.broadcast(optimizer.momentum_buffer, src=0)
-            if hasattr(optimizer, "mark_started"):
-                optimizer.mark_started()
+        _broadcast_optimizer(optimizer, rank, bdev, flat)
     return int(flag[1]), (str(latest) if latest is not None else "(broadcast from rank 0)")
+
+
+def _broadcast_optimizer(optimizer, rank: int, bdev, flat):
+    """Rank 0's optimizer state to every rank, through the optimizer protocol:
+    ``param_groups[0]`` (one object broadcast; an optimizer with ``state_counter()`` - AdamW's
+    step number - sends it in the same call), then ``state_buffers()``: named flat tensors,
+    all present or all ``None``, one broadcast each in the order given (SGD: the momentum
+    buffer alone, as before this protocol existed)."""
+    counted = hasattr(optimizer, "state_counter")
+    hp = [optimizer.param_groups[0] if rank == 0 else None]
+    if counted:
+        hp.append(optimizer.state_counter() if rank == 0 else None)
+    dist.broadcast_object_list(hp, src=0)
+    optimizer.param_groups[0].update(hp[0])
+    if hasattr(optimizer, "hyper_changed"):
+        optimizer.hyper_changed()
+    bufs = optimizer.state_buffers()
+    has = torch.tensor([1 if all(b is not None for b in bufs.values()) else 0], device=bdev)
+    dist.broadcast(has, src=0)
+    if int(has) == 1:
+        for name, buf in bufs.items():
+            if buf is None:
+                buf = torch.zeros_like(flat.params)
+                optimizer.set_state_buffer(name, buf)
+            dist.broadcast(buf, src=0)
+        if hasattr(optimizer, "mark_started"):
+            optimizer.mark_started()
+    if counted:
+        optimizer.set_state_counter(int(hp[1]))
