@@ -87,7 +87,33 @@ void xgmi_allreduce_pair(const BwdXar& x, hipStream_t s) {
   hipLaunchKernelGGL(xgmi_allreduce_pair_kernel, dim3(x.nblk0 + x.nblk1), dim3(XGMI_THREADS), 0, s, x);
 }
 
+// Loopback (tests/test_xgmi_loopback_gpu.py): N virtual ranks of one channel side by side in
+// one launch, each rank's arguments in device memory as for the pair kernel.  Rank v's blocks
+// are [v * nblk, (v + 1) * nblk); the ranks meet at the body's own barriers, so the launcher
+// keeps the grid small enough to be resident as a whole.
+template <bool WT>
+__global__ __launch_bounds__(XGMI_THREADS) void xgmi_allreduce_group_kernel(const XgmiArgs* args, int nblk) {
+  __shared__ unsigned s_sh[2];
+  __shared__ __attribute__((aligned(16))) int s_raw[sizeof(XgmiArgs) / 4];
+  const int v = (int)blockIdx.x / nblk;
+  {
+    const int* src = reinterpret_cast<const int*>(args + v);
+    for (int i = threadIdx.x; i < (int)(sizeof(XgmiArgs) / 4); i += XGMI_THREADS) s_raw[i] = src[i];
+  }
+  __syncthreads();
+  xgmi_allreduce_body<WT>(*reinterpret_cast<const XgmiArgs*>(s_raw), (int)blockIdx.x - v * nblk, nblk, s_sh);
+}
+
+bool xgmi_allreduce_group(const XgmiArgs* args, int world, int nblk, bool wt, hipStream_t s) {
+  if (world < 1 || world > XGMI_MAX_RANKS || nblk < 1 || world * nblk > XGMI_GROUP_MAX_BLOCKS) return false;
+  if (wt) hipLaunchKernelGGL(xgmi_allreduce_group_kernel<true>, dim3(world * nblk), dim3(XGMI_THREADS), 0, s, args, nblk);
+  else hipLaunchKernelGGL(xgmi_allreduce_group_kernel<false>, dim3(world * nblk), dim3(XGMI_THREADS), 0, s, args, nblk);
+  return true;
+}
+
 long xgmi_slice(long n, int world) { return (((n + world - 1) / world) + 3) & ~3L; }
+
+long xgmi_stage_floats(long n, int world, bool oneshot) { return oneshot ? (n + 3) & ~3L : xgmi_slice(n, world); }
 
 int xgmi_blocks(long n, int world, bool oneshot) {
   const long quads = ((oneshot ? n : xgmi_slice(n, world)) + 3) / 4;

@@ -441,7 +441,17 @@ struct XgmiArgs {
 };
 long xgmi_slice(long n, int world);  // two-shot slice: n / world rounded up to whole quads
 int xgmi_blocks(long n, int world, bool oneshot = false);
+// floats of ONE parity of a channel's stage buffer (whole quads): the rank's slice, or for a
+// one-shot channel the whole bucket; the buffer holds two parities
+long xgmi_stage_floats(long n, int world, bool oneshot);
 void xgmi_allreduce(const XgmiArgs& a, int blocks, hipStream_t s);
+// Loopback launch (XgmiLoopback, tests): `world` virtual ranks x one channel in ONE launch on
+// one GPU.  Block b runs the body as block b % nblk of rank b / nblk from args[b / nblk]
+// (device memory).  The ranks' barriers wait for each other inside the launch, so every block
+// must be resident at once: more than XGMI_GROUP_MAX_BLOCKS blocks are refused (returns false
+// without launching).  wt: the body's write-through build (the step head's merge_allreduce_role).
+constexpr int XGMI_GROUP_MAX_BLOCKS = 64;
+bool xgmi_allreduce_group(const XgmiArgs* args, int world, int nblk, bool wt, hipStream_t s);
 
 // In-launch bucket all-reduce of the multi-GPU level-3 step (engine dist_mode 2,
 // conv3x3.hip XAR): role blocks at the HEAD of the conv backward grid run the direct xGMI

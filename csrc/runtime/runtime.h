@@ -70,6 +70,19 @@ class Comm {
 // One channel per gradient bucket (a fixed [off, off + n) range of the gradient buffer);
 // see xgmi.cpp / kernels/allreduce.hip.  Producers of a bucket must write it with
 // system-scope stores (peers read it over xGMI right after the kernel boundary).
+// What one rank's kernel arguments of a channel are filled from: the bucket, and every rank's
+// data / stage / signal pointers as this rank addresses them.
+struct XgmiPlan {
+  long off, n, slice;
+  bool oneshot;
+  float* const* data;
+  float* const* stage;
+  unsigned* const* sig;
+};
+// the one place that fills XgmiArgs (XgmiComm::make_args and XgmiLoopback::all_reduce)
+XgmiArgs xgmi_fill_args(const XgmiPlan& c, int rank, int world, double timeout_s, const SgdArgs& sgd, float* params,
+                        float* mbuf, const ShadowSet& sh, int* step_ctr, float scale, bool publish, float prescale);
+
 class XgmiComm {
  public:
   XgmiComm(int rank, int world, int device);
@@ -139,6 +152,59 @@ class XgmiComm {
   };
   std::vector<PairArgs> pair_cache_;
   int* pair_done_ = nullptr;  // the pair launch's last-block count (zeroed before each launch)
+};
+
+// `world` virtual ranks of the all-reduce on ONE GPU in one process: every call is one launch
+// (xgmi_allreduce_group) in which each rank's blocks run the production kernel body from
+// arguments filled like XgmiComm's, against the other ranks' blocks of the same launch.  The
+// arithmetic, index mapping and barrier protocol of every world size run deterministically in
+// milliseconds (tests/test_xgmi_loopback_gpu.py); links, IPC mappings and skew between
+// ranks' launches stay with the multi-process tests.  The caller owns every data and stage
+// buffer (so a test can put guard bands round them) and keeps them alive.
+class XgmiLoopback {
+ public:
+  static constexpr double kTimeoutS = 2.0;  // peers are co-resident: a correct barrier waits microseconds
+  struct RankBuffers {  // one virtual rank's fused-SGD operands (see XgmiArgs)
+    float* params = nullptr;
+    float* mbuf = nullptr;
+    ShadowSet sh{};
+    int* step_ctr = nullptr;
+  };
+  XgmiLoopback(int world, int device);
+  ~XgmiLoopback();
+  XgmiLoopback(const XgmiLoopback&) = delete;
+  XgmiLoopback& operator=(const XgmiLoopback&) = delete;
+  void set_data(int rank, float* data, long numel);  // may be called again between calls
+  // blocks: most blocks per rank (0: xgmi_blocks); world * blocks(channel) <= XGMI_GROUP_MAX_BLOCKS.
+  // stage[r]: >= 2 * xgmi_stage_floats(n, world, oneshot) floats, 16-byte aligned
+  int add_channel(long off, long n, bool oneshot, int blocks, const std::vector<float*>& stage,
+                  const std::vector<long>& stage_numel);
+  long slice(int channel) const { return ch_.at(channel).slice; }
+  int blocks(int channel) const { return ch_.at(channel).blocks; }
+  bool oneshot(int channel) const { return ch_.at(channel).oneshot; }
+  int channels() const { return (int)ch_.size(); }
+  int world() const { return world_; }
+  long data_numel(int rank) const { return numel_[rank]; }
+  void all_reduce(int channel, hipStream_t s, const SgdArgs& sgd, const std::vector<RankBuffers>& per_rank,
+                  float scale, bool publish, float prescale, bool wt);
+  unsigned error_flags() const;                      // the first non-zero error word of any rank
+  unsigned seq(int channel, int rank, int blk) const;  // a block's call counter
+  void set_timeout(double seconds) { timeout_s_ = seconds; }
+
+ private:
+  struct Channel {
+    long off = 0, n = 0, slice = 0;
+    int blocks = 1;
+    bool oneshot = false;
+    float* stage[XGMI_MAX_RANKS] = {};
+    unsigned* sig[XGMI_MAX_RANKS] = {};
+  };
+  int world_, device_;
+  float* data_[XGMI_MAX_RANKS] = {};
+  long numel_[XGMI_MAX_RANKS] = {};
+  std::vector<Channel> ch_;
+  XgmiArgs* dev_args_ = nullptr;
+  double timeout_s_ = kTimeoutS;
 };
 
 // ---------------------------------------------------------------- gradient reducer

@@ -61,7 +61,7 @@ int XgmiComm::add_channel(long off, long n, bool oneshot, int grid_cap) {
   if (const char* e = std::getenv("DDP_AMD_XGMI_GRID_CAP")) c.blocks = std::max(1, std::min(c.blocks, std::atoi(e)));
   if (c.blocks > XGMI_MAX_BLOCKS) throw std::runtime_error("xgmi: bucket too large for one channel");
   if (n * 4 >= (1L << 31)) throw std::runtime_error("xgmi: bucket over 2 GiB (32-bit buffer offsets)");
-  const long stage = oneshot ? (n + 3) & ~3L : c.slice;  // per parity, whole quads
+  const long stage = xgmi_stage_floats(n, world_, oneshot);  // per parity, whole quads
   DDP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c.stage_local), sizeof(float) * 2 * stage));
   DDP_HIP_CHECK(hipExtMallocWithFlags(reinterpret_cast<void**>(&c.sig_local),
                                       sizeof(unsigned) * XGMI_SIG_WORDS, hipDeviceMallocUncached));
@@ -147,16 +147,13 @@ void XgmiComm::all_reduce(int channel, hipStream_t s, float scale, bool publish,
   all_reduce_sgd(channel, s, SgdArgs{}, nullptr, nullptr, ShadowSet{}, nullptr, scale, publish, prescale);
 }
 
-XgmiArgs XgmiComm::make_args(int channel, const SgdArgs& sgd, float* params, float* mbuf, const ShadowSet& sh,
-                              int* step_ctr, float scale, bool publish, float prescale) const {
-  if (!imported_) throw std::runtime_error("xgmi: import_handles first");
-  if (channel < 0 || channel >= (int)ch_.size()) throw std::runtime_error("xgmi: bad channel");
-  const Channel& c = ch_[channel];
+XgmiArgs xgmi_fill_args(const XgmiPlan& c, int rank, int world, double timeout_s, const SgdArgs& sgd, float* params,
+                        float* mbuf, const ShadowSet& sh, int* step_ctr, float scale, bool publish, float prescale) {
   if (prescale != 1.f && !publish && !c.oneshot)
     throw std::runtime_error("xgmi: prescale needs the publish pass (or a one-shot channel)");
   XgmiArgs a{};
-  for (int r = 0; r < world_; ++r) {
-    a.data[r] = data_peer_[r];
+  for (int r = 0; r < world; ++r) {
+    a.data[r] = c.data[r];
     a.stage[r] = c.stage[r];
     a.sig[r] = c.sig[r];
   }
@@ -167,9 +164,9 @@ XgmiArgs XgmiComm::make_args(int channel, const SgdArgs& sgd, float* params, flo
   a.publish = publish ? 1 : 0;
   a.scale = scale;
   a.prescale = prescale;
-  a.rank = rank_;
-  a.world = world_;
-  a.timeout_ticks = (unsigned long long)(timeout_s_ * 1e8);
+  a.rank = rank;
+  a.world = world;
+  a.timeout_ticks = (unsigned long long)(timeout_s * 1e8);
   a.sgd = sgd;
   a.params = params;
   a.mbuf = mbuf;
@@ -177,6 +174,15 @@ XgmiArgs XgmiComm::make_args(int channel, const SgdArgs& sgd, float* params, flo
   a.step_ctr = step_ctr;
   if (sgd.update && !params) throw std::runtime_error("xgmi: fused SGD needs the parameter buffer");
   return a;
+}
+
+XgmiArgs XgmiComm::make_args(int channel, const SgdArgs& sgd, float* params, float* mbuf, const ShadowSet& sh,
+                              int* step_ctr, float scale, bool publish, float prescale) const {
+  if (!imported_) throw std::runtime_error("xgmi: import_handles first");
+  if (channel < 0 || channel >= (int)ch_.size()) throw std::runtime_error("xgmi: bad channel");
+  const Channel& c = ch_[channel];
+  const XgmiPlan plan{c.off, c.n, c.slice, c.oneshot, data_peer_, c.stage, c.sig};
+  return xgmi_fill_args(plan, rank_, world_, timeout_s_, sgd, params, mbuf, sh, step_ctr, scale, publish, prescale);
 }
 
 void XgmiComm::all_reduce_sgd(int channel, hipStream_t s, const SgdArgs& sgd, float* params,
@@ -224,6 +230,98 @@ unsigned XgmiComm::error_flags() const {
     if (v) return v;  // the first failed channel's code (codes must not be OR-ed together)
   }
   return 0;
+}
+
+// ------------------------------------------------------------------------------- loopback
+XgmiLoopback::XgmiLoopback(int world, int device) : world_(world), device_(device) {
+  if (world < 1 || world > XGMI_MAX_RANKS)
+    throw std::runtime_error("xgmi loopback: world size must be 1.." + std::to_string(XGMI_MAX_RANKS));
+  DDP_HIP_CHECK(hipSetDevice(device));
+  DDP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dev_args_), sizeof(XgmiArgs) * XGMI_MAX_RANKS));
+}
+
+XgmiLoopback::~XgmiLoopback() {
+  if (process_exiting()) return;
+  if (dev_args_) hipFree(dev_args_);
+  for (auto& c : ch_)
+    for (int r = 0; r < world_; ++r)
+      if (c.sig[r]) hipFree(c.sig[r]);
+}
+
+void XgmiLoopback::set_data(int rank, float* data, long numel) {
+  if (rank < 0 || rank >= world_) throw std::runtime_error("xgmi loopback: bad rank");
+  data_[rank] = data;
+  numel_[rank] = numel;
+}
+
+int XgmiLoopback::add_channel(long off, long n, bool oneshot, int blocks, const std::vector<float*>& stage,
+                              const std::vector<long>& stage_numel) {
+  if (off < 0 || n < 1) throw std::runtime_error("xgmi loopback: bad bucket");
+  if (n * 4 >= (1L << 31)) throw std::runtime_error("xgmi: bucket over 2 GiB (32-bit buffer offsets)");
+  if ((int)stage.size() != world_ || (int)stage_numel.size() != world_)
+    throw std::runtime_error("xgmi loopback: need one stage buffer per rank");
+  Channel c;
+  c.off = off;
+  c.n = n;
+  c.oneshot = oneshot;
+  c.slice = xgmi_slice(n, world_);
+  c.blocks = xgmi_blocks(n, world_, oneshot);
+  if (blocks > 0) c.blocks = std::min(c.blocks, blocks);
+  // the virtual ranks wait for each other inside one launch: the whole grid must be resident
+  if (world_ * c.blocks > XGMI_GROUP_MAX_BLOCKS)
+    throw std::runtime_error("xgmi loopback: world * blocks exceeds " + std::to_string(XGMI_GROUP_MAX_BLOCKS) +
+                             " (give add_channel a smaller block count)");
+  const long need = 2 * xgmi_stage_floats(n, world_, oneshot);
+  for (int r = 0; r < world_; ++r) {
+    if (!stage[r] || stage_numel[r] < need) throw std::runtime_error("xgmi loopback: stage buffer too small");
+    c.stage[r] = stage[r];
+  }
+  for (int r = 0; r < world_; ++r) {
+    DDP_HIP_CHECK(hipExtMallocWithFlags(reinterpret_cast<void**>(&c.sig[r]), sizeof(unsigned) * XGMI_SIG_WORDS,
+                                        hipDeviceMallocUncached));
+    DDP_HIP_CHECK(hipMemset(c.sig[r], 0, sizeof(unsigned) * XGMI_SIG_WORDS));
+  }
+  DDP_HIP_CHECK(hipDeviceSynchronize());
+  ch_.push_back(c);
+  return (int)ch_.size() - 1;
+}
+
+void XgmiLoopback::all_reduce(int channel, hipStream_t s, const SgdArgs& sgd, const std::vector<RankBuffers>& per_rank,
+                              float scale, bool publish, float prescale, bool wt) {
+  if (channel < 0 || channel >= (int)ch_.size()) throw std::runtime_error("xgmi: bad channel");
+  if ((int)per_rank.size() != world_) throw std::runtime_error("xgmi loopback: need one buffer set per rank");
+  const Channel& c = ch_[channel];
+  for (int r = 0; r < world_; ++r)
+    if (!data_[r] || c.off + c.n > numel_[r]) throw std::runtime_error("xgmi: channel outside the data buffer");
+  const XgmiPlan plan{c.off, c.n, c.slice, c.oneshot, data_, c.stage, c.sig};
+  XgmiArgs host[XGMI_MAX_RANKS];
+  for (int r = 0; r < world_; ++r)
+    host[r] = xgmi_fill_args(plan, r, world_, timeout_s_, sgd, per_rank[r].params, per_rank[r].mbuf, per_rank[r].sh,
+                             per_rank[r].step_ctr, scale, publish, prescale);
+  // (a blocking copy after the stream drained: the previous launch may still read dev_args_)
+  DDP_HIP_CHECK(hipStreamSynchronize(s));
+  DDP_HIP_CHECK(hipMemcpy(dev_args_, host, sizeof(XgmiArgs) * world_, hipMemcpyHostToDevice));
+  if (!xgmi_allreduce_group(dev_args_, world_, c.blocks, wt, s))
+    throw std::runtime_error("xgmi loopback: grid refused");
+  DDP_HIP_CHECK(hipGetLastError());
+}
+
+unsigned XgmiLoopback::error_flags() const {
+  for (const auto& c : ch_)
+    for (int r = 0; r < world_; ++r) {
+      unsigned v = 0;
+      DDP_HIP_CHECK(hipMemcpy(&v, c.sig[r] + XGMI_ERR_OFF, sizeof(v), hipMemcpyDeviceToHost));
+      if (v) return v;
+    }
+  return 0;
+}
+
+unsigned XgmiLoopback::seq(int channel, int rank, int blk) const {
+  const Channel& c = ch_.at(channel);
+  if (rank < 0 || rank >= world_ || blk < 0 || blk >= c.blocks) throw std::runtime_error("xgmi loopback: bad rank / block");
+  unsigned v = 0;
+  DDP_HIP_CHECK(hipMemcpy(&v, c.sig[rank] + XGMI_SEQ_OFF + blk, sizeof(v), hipMemcpyDeviceToHost));
+  return v;
 }
 
 }  // namespace ddp_amd

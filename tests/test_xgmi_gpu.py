@@ -2,13 +2,18 @@
 
 RCCL refuses two ranks on one GPU ("Duplicate GPU detected"), but the xGMI path only needs
 IPC mappings, which also work between processes sharing a device.  So these tests run 2
-ranks on cuda:0 of the single-GPU test box (gloo process group for bootstrap only) and
-exercise the exact kernel, protocol and engine code that runs across 8 GPUs.  Two, not
-more: the kernel's barriers spin until the peers' blocks arrive, which on ONE GPU needs
+(some also 3) ranks on cuda:0 of the single-GPU test box (gloo process group for bootstrap
+only) and exercise the exact kernel, protocol and engine code that runs across 8 GPUs.  Not
+more than 3: the kernel's barriers spin until the peers' blocks arrive, which on ONE GPU needs
 every rank's kernel resident at once - the GPU runs two processes' queues side by side,
-but from three on it time-slices them and a barrier can wait seconds (measured with
+but with more it time-slices them and a barrier can wait seconds (measured with
 scripts/xgmi_probe.py: correct sums, 17-40 s stalls).  With one GPU per rank (the real
 deployment) every rank's kernel has its own device.
+
+World sizes above 3 and the sweep over bucket lengths, offsets, grids and fused-SGD options
+live in tests/test_xgmi_loopback_gpu.py: N = 1..8 virtual ranks of the same kernel body in one
+launch of one process.  What that cannot show - real IPC mappings, skew between the ranks'
+launches across calls, the pair kernel's completion count - is covered here.
 """
 import os
 
