@@ -383,6 +383,23 @@ void sgd_step(float* p, const float* g, float* mbuf, long n, const SgdArgs& a, c
 void adamw_step(float* p, const float* g, float* mbuf, float* vbuf, long n, const AdamArgs& a,
                 const ShadowSet& sh, hipStream_t s, const float* gscale, const float* coef, int n_coef,
                 SchedState* sched);
+// ---- LARS: per-tensor norms / trust ratios and the update that reads them (lars.hip) ----
+constexpr int LARS_THREADS = 256, LARS_ITEM = 4096, LARS_CHUNK = 64, LARS_MAX_BLOCKS = 2048;
+constexpr int LARS_MAX_SEGS = 4095;  // n_seg + 1 {ratio, wd} pairs fit 32 KiB of LDS; cmap entries are int16
+int seg_sqnorm_blocks(int n_items);  // grid: a function of the table alone
+// partials: 2 n_items floats; ticket: one int, zero before the first launch; sums: 2 n_seg
+// floats {S_w, S_g}; trust: 4 (n_seg + 1) floats {ratio, wd, wn, gn}, 16-byte aligned - the
+// launch writes entries [0, n_seg), entry n_seg is the null segment {1, 0, 0, 0} the host wrote.
+// gscale != nullptr: the gradient norms are those of the clipped gradient (gn * gscale[0]).
+void seg_sqnorm(const float* w, const float* g, long n, const LarsItem* items, int n_items, const LarsSeg* segs,
+                int n_seg, float* partials, int* ticket, float* sums, float* trust, float trust_coef, float eps,
+                const float* gscale, hipStream_t s);
+// One LARS step over flat fp32 params / grads / momentum: sgd_step with a.weight_decay
+// replaced by the per-tensor {ratio, wd} of trust[cmap[i / 64]] (cmap: ceil(n / 64) entries in
+// [0, n_seg]).  gscale / lr_table / sched as sgd_step.
+void lars_step(float* p, const float* g, float* mbuf, long n, const SgdArgs& a, const ShadowSet& sh,
+               const short* cmap, const float* trust, int n_seg, hipStream_t s, const float* gscale = nullptr,
+               const float* lr_table = nullptr, int n_table = 0, SchedState* sched = nullptr);
 // ---- global gradient norm / clip coefficient (grad_norm.hip) --------------------------
 constexpr int GN_THREADS = 256, GN_QUADS = 4, GN_MAX_BLOCKS = 1024;
 struct ClipStats {

@@ -84,6 +84,19 @@ struct AdamArgs {
   int maximize, update;
 };
 
+// LARS segment table (lars.hip; built by ops/lars.py lars_layout from the parameter shapes).
+// One LarsSeg per tensor: it begins at flat element 64 * begin_chunk, its work items are
+// items[item0 .. item0 + n_items); adapt == 0: excluded from the trust ratio (ratio 1).
+struct LarsSeg {
+  int begin_chunk, numel, item0, n_items;
+  float wd;
+  int adapt, pad0, pad1;
+};
+// One piece of tensor `seg` (its k-th): len <= LARS_ITEM elements from 64 * begin_chunk
+struct LarsItem {
+  int begin_chunk, len, seg, k;
+};
+
 // diagnostic phase-stamp kernel ids / buffer geometry (common.h DDP_STAMP)
 enum { STAMP_K_CONV_FWD = 0, STAMP_K_FC_BWD = 1, STAMP_K_DGRAD = 2, STAMP_K_WGRAD = 3,
        STAMP_K_GRAD_REDUCE = 4, STAMP_K_SGD = 5, STAMP_K_XENT = 6, STAMP_K_CONV1 = 7,

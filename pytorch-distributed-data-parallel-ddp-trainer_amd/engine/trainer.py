@@ -32,7 +32,7 @@ from ..data import (DeviceImageLoader, DeviceImages, DeviceMNIST, DeviceMNISTLoa
                     load_mnist, synthetic_imagenet, synthetic_imagenet_test)
 from ..models import SimpleCNN, resnet18
 from ..models.layers import buffer_space, flat_space
-from ..ops import CrossEntropyLoss, FusedAdamW, FusedSGD
+from ..ops import CrossEntropyLoss, FusedAdamW, FusedLARS, FusedSGD
 from ..parallel import DistributedDataParallel as DDP
 from ..parallel import cleanup, local_rank, native_comm, setup
 from ..utils.checkpoint import resume, save_checkpoint
@@ -85,10 +85,13 @@ class TrainOptions:
     lr_min: float = 0.0               # cosine / linear: the rate the decay ends at
     lr_step_epochs: int = 0           # step: multiply the rate by lr_gamma every N epochs
     lr_gamma: float = 0.1
-    optimizer: str = "sgd"            # sgd | adamw (adamw: module/CPU path)
+    optimizer: str = "sgd"            # sgd | adamw | lars (adamw, lars: module/CPU path)
     beta1: float = 0.9                # adamw
     beta2: float = 0.999              # adamw
     adam_eps: float = 1e-8            # adamw
+    trust_coef: float = 1e-3          # lars: the trust ratio's coefficient
+    lars_eps: float = 1e-8            # lars: the trust ratio denominator's epsilon
+    lars_exclude: str = "1d"          # lars: 1d (BatchNorm scales, biases: ratio 1, no decay) | none
 
 
 def validate_options(opts: TrainOptions):
@@ -112,8 +115,13 @@ def validate_options(opts: TrainOptions):
         raise ValueError("--warmup_steps must be >= 0")
     if opts.lr_schedule == "step" and opts.lr_step_epochs < 1:
         raise ValueError("--lr_schedule step needs --lr_step_epochs N >= 1")
-    if opts.optimizer not in ("sgd", "adamw"):
-        raise ValueError(f"--optimizer must be sgd or adamw, got {opts.optimizer!r}")
+    if opts.optimizer not in ("sgd", "adamw", "lars"):
+        raise ValueError(f"--optimizer must be sgd, adamw or lars, got {opts.optimizer!r}")
+    if opts.optimizer == "lars":
+        if not opts.trust_coef > 0 or opts.lars_eps < 0:
+            raise ValueError("--trust_coef must be positive and --lars_eps >= 0")
+        if opts.lars_exclude not in ("1d", "none"):
+            raise ValueError(f"--lars_exclude must be 1d or none, got {opts.lars_exclude!r}")
     if opts.optimizer == "adamw" and opts.momentum != 0:
         raise ValueError("--momentum is SGD's; --optimizer adamw takes --beta1 / --beta2 / --adam_eps")
     if (opts.device or "").lower() == "gpu":  # the fused engine is certain: refuse before any process starts
@@ -133,6 +141,10 @@ def check_fused_engine_options(opts: TrainOptions, fused: bool):
         raise ValueError("--lr_schedule / --warmup_steps need the module path (--engine module) or the CPU "
                          "path; the fused engine bakes the learning rate into its kernels' arguments and "
                          "into its captured step graphs")
+    if fused and opts.optimizer == "lars":
+        raise ValueError("--optimizer lars needs the module path (--engine module) or the CPU path; the "
+                         "fused engine applies SGD inside the kernels that finish each gradient, before "
+                         "any tensor's gradient norm exists")
     if fused and opts.optimizer != "sgd":
         raise ValueError("--optimizer adamw needs the module path (--engine module) or the CPU path; the "
                          "fused engine applies SGD inside the kernels that finish each gradient and keeps "
@@ -240,6 +252,12 @@ def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
         opt = FusedAdamW(model, lr=opts.lr, betas=(opts.beta1, opts.beta2), eps=opts.adam_eps,
                          weight_decay=opts.weight_decay, max_grad_norm=opts.clip_grad_norm or None,
                          lr_schedule=build_lr_schedule(opts, epochs, per_epoch))
+    elif opts.optimizer == "lars":
+        opt = FusedLARS(model, lr=opts.lr, momentum=opts.momentum, weight_decay=opts.weight_decay,
+                        trust_coef=opts.trust_coef, eps=opts.lars_eps,
+                        exclude=None if opts.lars_exclude == "none" else "1d",
+                        max_grad_norm=opts.clip_grad_norm or None,
+                        lr_schedule=build_lr_schedule(opts, epochs, per_epoch))
     else:
         opt = FusedSGD(model, lr=opts.lr, momentum=opts.momentum, weight_decay=opts.weight_decay,
                        max_grad_norm=opts.clip_grad_norm or None,
@@ -336,6 +354,8 @@ def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
                         samples_processed(nsteps, batch_size, len(sampler)), ev,
                         clip=opt.grad_clip_stats() if opts.metrics_json and rank == 0 else None,
                         lr=opt.current_lr() if opts.metrics_json and rank == 0 and opt.lr_schedule is not None
+                        else None,
+                        trust=opt.trust_stats() if opts.metrics_json and rank == 0 and opts.optimizer == "lars"
                         else None)
 
         if opts.verify_replicas and world_size > 1:
@@ -612,11 +632,12 @@ def samples_processed(nsteps: int, batch: int, samples_per_rank: int) -> int:
     return min(nsteps * batch, samples_per_rank)
 
 
-def _record_metrics(opts, rank, ws, epoch, nsteps, batch, dt, samples, ev=None, clip=None, lr=None):
+def _record_metrics(opts, rank, ws, epoch, nsteps, batch, dt, samples, ev=None, clip=None, lr=None, trust=None):
     """``samples``: images this rank processed in the epoch (:func:`samples_processed`);
     ``ev``: the epoch's evaluation totals, when it ran (eval_loss / eval_accuracy keys);
     ``clip``: FusedSGD.grad_clip_stats() with --clip_grad_norm (grad_norm: the last step's
-    norm; clipped_steps: steps clipped so far in this run)."""
+    norm; clipped_steps: steps clipped so far in this run); ``trust``: FusedLARS.trust_stats()
+    (trust_ratio_min / trust_ratio_max over the adapted tensors, the epoch's last step)."""
     if not opts.metrics_json or rank != 0:
         return
     import json
@@ -632,5 +653,9 @@ def _record_metrics(opts, rank, ws, epoch, nsteps, batch, dt, samples, ev=None, 
         rec["grad_norm"], rec["clipped_steps"] = clip["total_norm"], clip["clipped"]
     if lr is not None:
         rec["lr"] = lr  # with a schedule: FusedSGD.current_lr() at the end of the epoch, the next step's rate
+    if trust:
+        ratios = [t["ratio"] for t in trust.values() if t["adapted"]]
+        if ratios:
+            rec["trust_ratio_min"], rec["trust_ratio_max"] = min(ratios), max(ratios)
     with open(opts.metrics_json, "a") as f:
         f.write(json.dumps(rec) + "\n")

@@ -290,3 +290,141 @@ def sqnorm_bound(n, sumsq64):
     e_n = (gk / 2 + U) * (1 + gk)
     e_c = (e_n + 3 * U) * (1 + e_n + 3 * U) / (1 - e_n - 3 * U)
     return gk * sumsq64, e_n * float(np.sqrt(sumsq64)), e_c
+
+
+# ------------------------------------------------------------ LARS: per-tensor norms, trust ratio
+LARS_ITEM, LARS_CHUNK = 4096, 64  # csrc/kernels/launchers.h
+
+
+def lars_items(numel):
+    """Work items of a tensor: ceil(numel / LARS_ITEM)."""
+    return -(-int(numel) // LARS_ITEM)
+
+
+def replay_seg_sqnorm(x32):
+    """The float32 sum of squares of one tensor's elements x32 in seg_sqnorm_kernel's documented
+    order (csrc/kernels/lars.hip, header): per item the 256 threads' folded squares, the wave
+    trees and the block sum; then lane j's sequential sum of the item partials j, j + 64, ...
+    and one more wave tree."""
+    x32 = np.asarray(x32, dtype=np.float32).reshape(-1)
+    k_n = lars_items(x32.size)
+    buf = np.zeros(max(k_n, 1) * LARS_ITEM, dtype=np.float32)  # elements past len count as +0.0f
+    buf[:x32.size] = x32
+    sq = _fma32(buf, np.zeros_like(buf)).reshape(max(k_n, 1), 4, GN_THREADS, 4)  # [item][u][thread][c]
+    s = ((sq[..., 0] + sq[..., 1]).astype(np.float32) + (sq[..., 2] + sq[..., 3]).astype(np.float32)).astype(np.float32)
+    th = ((s[:, 0] + s[:, 1]).astype(np.float32) + (s[:, 2] + s[:, 3]).astype(np.float32)).astype(np.float32)
+    part = _block_sum(th)[:k_n]  # [item]
+    lanes = np.zeros(64, dtype=np.float32)
+    for k in range(k_n):  # lane k % 64 adds its partials in item order
+        lanes[k % 64] = np.float32(lanes[k % 64] + part[k])
+    return np.float32(_wave_tree(lanes.reshape(1, 64))[0])
+
+
+def seg_sqnorm_chain(numel):
+    """Longest chain of roundings between a square and a tensor's sum (lars.hip header)."""
+    return 1 + 2 + 2 + 6 + 3 + -(-lars_items(numel) // 64) + 6
+
+
+def trust_ratio32(sw32, sg32, wd, trust_coef, eps, adapt=True, coef=None):
+    """(wn, gn, ratio) in float32 from the float32 sums of squares, as step 6 of
+    seg_sqnorm_kernel: correctly rounded roots, gn * coef with clipping, then
+    fdiv_rn(trust_coef * wn, fmaf(wd, wn, gn) + eps) if adapt and wn > 0 and gn > 0, else 1."""
+    f = np.float32
+    wn = f(np.sqrt(np.float64(f(sw32))))
+    gn = f(np.sqrt(np.float64(f(sg32))))
+    if coef is not None:
+        gn = f(gn * f(coef))
+    ratio = f(1.0)
+    if adapt and wn > 0 and gn > 0:
+        den = f(np.longdouble(f(wd)) * np.longdouble(wn) + np.longdouble(gn))  # one fma
+        den = f(den + f(eps))
+        ratio = f(f(f(trust_coef) * wn) / den)
+    return wn, gn, ratio
+
+
+def trust_ratio_bound(numel, clip=False):
+    """A-priori relative bound of the fp32 trust ratio of a tensor of numel elements.
+
+    Each sum of squares has non-negative terms behind a chain of k = seg_sqnorm_chain(numel)
+    roundings: relative gamma_k = k u / (1 - k u); the correctly rounded root halves it and adds
+    one rounding: e_n = (gamma_k / 2 + u)(1 + gamma_k) per norm (as sqnorm_bound) - half the chain
+    length of each norm's summation.  The handful of roundings of the ratio: the numerator's
+    product (u); gn's clip multiply (u, with clipping); the denominator's fma and the add of eps
+    (2 u; every term is non-negative, so relative errors do not grow); the division (u).  First
+    order e_n + u for the numerator, e_n + 3 u for the denominator; second-order terms are
+    covered by the factor 1 + 2^-10."""
+    k = seg_sqnorm_chain(numel)
+    gk = k * U / (1.0 - k * U)
+    e_n = (gk / 2 + U) * (1 + gk)
+    return (2 * e_n + (6 if clip else 5) * U) * (1 + 2.0 ** -10)
+
+
+def lars_reference(w, g, m, numels_begins, wds, adapts, lr, momentum, dampening, nesterov, maximize, first,
+                   trust_coef, eps, coef=None):
+    """The LARS rule (ops/lars.py) in float64 over flat float32 inputs, and the a-priori
+    per-element bounds of the fp32 evaluation in lars.hip's order.
+
+    ``numels_begins``: [(begin, numel)] per tensor; ``m``: momentum buffer or None; ``coef``: the
+    fp32 clip coefficient or None; every scalar is taken at its float32 value.  Returns
+    ``(p64, m64, ratios64, bound_p, bound_m)``; elements outside every tensor keep p and get
+    zero bounds.
+
+    Bounds, u = 2^-24, rho_i = trust_ratio_bound of the tensor, first order, each decay / momentum
+    multiply-add counted as two roundings (the kernel fuses them into one; the torch path does
+    not), magnitudes taken as sums of absolute values:
+      d0 = coef g:                   e0 = u |coef g|           (0 without clipping)
+      d1 = wd w + d0, A1 = |wd w| + |d0|:   e1 = e0 + 2 u A1   (e0 without decay)
+      d2 = d1 R, A2 = R A1:          e2 = R e1 + (rho + u) A2
+      buf = d2 (first step): eb = e2, Ab = A2; else buf = (1 - damp) d2 + mom m,
+        Ab = (1 - damp) A2 + |mom m|:  eb = (1 - damp) e2 + 3 u (1 - damp) A2 + 2 u |mom m|
+        (the fp32 constant 1 - damp, the product, the fma's rounding; mom m and the sum)
+      d3 = buf, or with nesterov d2 + mom buf, A3 = A2 + mom Ab:  e3 = e2 + mom eb + 2 u A3
+      p' = w - lr d3:                ep = lr e3 + u lr A3 + u (|w| + lr A3)
+    both multiplied by 1 + 2^-10 for the second-order terms.  Without momentum d3 = d2."""
+    f64 = np.float64
+    w64, g64 = np.asarray(w, dtype=np.float32).astype(f64), np.asarray(g, dtype=np.float32).astype(f64)
+    m64 = None if m is None else np.asarray(m, dtype=np.float32).astype(f64)
+    lr, mom, damp = f64(np.float32(lr)), f64(np.float32(momentum)), f64(np.float32(dampening))
+    tc, ep, c = f64(np.float32(trust_coef)), f64(np.float32(eps)), None if coef is None else f64(np.float32(coef))
+    p_out, m_out = w64.copy(), (np.zeros_like(w64) if m64 is None else m64.copy())
+    bp, bm = np.zeros_like(w64), np.zeros_like(w64)
+    ratios = []
+    slack = 1 + 2.0 ** -10
+    for (b, n), wd, adapt in zip(numels_begins, wds, adapts):
+        sl = slice(b, b + n)
+        ww, gg = w64[sl], g64[sl]
+        wd = f64(np.float32(wd))
+        wn, gn = np.sqrt((ww * ww).sum()), np.sqrt((gg * gg).sum())
+        if c is not None:
+            gn = gn * c
+        R = tc * wn / (wd * wn + gn + ep) if (adapt and wn > 0 and gn > 0) else f64(1.0)
+        rho = trust_ratio_bound(n, c is not None) if (adapt and wn > 0 and gn > 0) else 0.0
+        ratios.append(R)
+        d0 = gg if c is None else gg * c
+        e0 = 0.0 if c is None else U * np.abs(d0)
+        if maximize:
+            d0 = -d0
+        A1 = np.abs(d0) + np.abs(wd * ww)
+        d1 = d0 + wd * ww
+        e1 = e0 + (2 * U * A1 if wd != 0 else 0.0)
+        d2, A2 = d1 * R, R * A1
+        e2 = R * e1 + (rho + U) * A2
+        if mom != 0:
+            if first:
+                buf, eb, Ab = d2, e2, A2
+            else:
+                mm = mom * m64[sl]
+                buf = (1 - damp) * d2 + mm
+                Ab = (1 - damp) * A2 + np.abs(mm)
+                eb = (1 - damp) * e2 + 3 * U * (1 - damp) * A2 + 2 * U * np.abs(mm)
+            m_out[sl], bm[sl] = buf, eb * slack
+            if nesterov:
+                d3, A3 = d2 + mom * buf, A2 + mom * Ab
+                e3 = e2 + mom * eb + 2 * U * A3
+            else:
+                d3, A3, e3 = buf, Ab, eb
+        else:
+            d3, A3, e3 = d2, A2, e2
+        p_out[sl] = ww - lr * d3
+        bp[sl] = (lr * e3 + U * lr * A3 + U * (np.abs(ww) + lr * A3)) * slack
+    return p_out, m_out, np.asarray(ratios), bp, bm

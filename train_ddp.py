@@ -44,14 +44,21 @@ def parse_args(argv=None):
     p.add_argument("--lr", type=float, default=0.01)
     p.add_argument("--momentum", type=float, default=0.0)
     p.add_argument("--weight_decay", type=float, default=0.0)
-    p.add_argument("--optimizer", choices=["sgd", "adamw"], default="sgd",
+    p.add_argument("--optimizer", choices=["sgd", "adamw", "lars"], default="sgd",
                    help="sgd: torch.optim.SGD semantics (--momentum); adamw: torch.optim.AdamW semantics "
                         "(--beta1 / --beta2 / --adam_eps, decoupled --weight_decay), one fused kernel whose "
                         "bias correction follows a device step counter, so --graph_module replays are exact "
-                        "(module/CPU path)")
+                        "(module/CPU path); lars: SGD with --momentum whose per-tensor decayed gradient is scaled "
+                        "by a trust ratio computed on the device (--trust_coef / --lars_eps / --lars_exclude; "
+                        "module/CPU path)")
     p.add_argument("--beta1", type=float, default=0.9, help="adamw: first-moment decay")
     p.add_argument("--beta2", type=float, default=0.999, help="adamw: second-moment decay")
     p.add_argument("--adam_eps", type=float, default=1e-8, help="adamw: the denominator's epsilon")
+    p.add_argument("--trust_coef", type=float, default=1e-3, help="lars: the trust ratio's coefficient")
+    p.add_argument("--lars_eps", type=float, default=1e-8, help="lars: the trust ratio denominator's epsilon")
+    p.add_argument("--lars_exclude", choices=["1d", "none"], default="1d",
+                   help="lars: 1d = parameters with ndim <= 1 (BatchNorm scales, biases) get ratio 1 and no "
+                        "weight decay; none = every tensor is adapted and decayed")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--log_every", type=int, default=100)
     p.add_argument("--graph_steps", type=int, default=100, help="steps per captured hipGraph")
@@ -133,7 +140,8 @@ def main(argv=None):
                         clip_grad_norm=a.clip_grad_norm, lr_schedule=a.lr_schedule,
                         warmup_steps=a.warmup_steps, lr_min=a.lr_min, lr_step_epochs=a.lr_step_epochs,
                         lr_gamma=a.lr_gamma, optimizer=a.optimizer, beta1=a.beta1, beta2=a.beta2,
-                        adam_eps=a.adam_eps,
+                        adam_eps=a.adam_eps, trust_coef=a.trust_coef, lars_eps=a.lars_eps,
+                        lars_exclude=a.lars_exclude,
                         stall=tuple(float(v) for v in a.stall_at.split(":")) if a.stall_at else None,
                         fault=tuple(int(v) for v in a.fault_at.split(":")) if a.fault_at else None)
     validate_options(opts)
