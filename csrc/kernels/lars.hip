@@ -2,7 +2,8 @@
 // tensor's decayed gradient is first scaled by that tensor's trust ratio.  Two launches per
 // step, both replayable by a captured graph: seg_sqnorm_kernel leaves every tensor's weight
 // norm, gradient norm and trust ratio in device memory, and lars_kernel<CLIP, DLR> - the
-// streaming structure of sgd_kernel (optim.hip), shadow refresh included - reads them there.
+// streaming pass of flat_step.h (flat_stream, shared with sgd_kernel and adamw_kernel), shadow
+// refresh included - reads them there.
 //
 // The segment table (ops/lars.py lars_layout; a function of the parameter shapes alone, so
 // the same on every GPU; every tensor begins on a 64-element boundary of the flat buffer):
@@ -38,8 +39,7 @@
 // (kernel_bounds.seg_sqnorm_chain).  In flight per thread and item: 4 + 4 independent
 // 16-byte loads, all issued before the first use (the clamp-and-zero form of grad_norm.hip).
 //
-// lars_kernel - geometry of sgd_kernel: 256 threads, one quad per thread per grid-stride
-// pass, grid min(max(ceil(n4 / 256), 1), 2048), the n % 4 tail on the first threads of block 0.
+// lars_kernel - geometry, the CLIP multiply and the schedule protocol: flat_step.h.
 // A quad lies in one 64-element chunk, so in one tensor: s = cmap[i / 64], {ratio, wd} =
 // trust[s].  Per element, all fp32, every line one rounding:
 //   d = g                    CLIP: d = g * gscale[0]; maximize: d = -d (exact)
@@ -49,18 +49,20 @@
 //   d = fmaf(momentum, buf, d) with nesterov, else buf)                      sgd_one's lines)
 //   w = fmaf(-lr, d, w)
 // With ratio = 1 the product is exact and the sequence is sgd_one's, bit for bit.  DLR: lr is
-// lr_table[min(t, n_table - 1)], t = sched->t, advanced inside the launch by the ticket
-// protocol of sgd_kernel<.., true>; a shadows-only launch (a.update == 0) takes no ticket.
+// lr_table[min(t, n_table - 1)], t = sched->t, advanced inside the launch; a shadows-only
+// launch (a.update == 0) is no optimizer step: it fills no table, reads no t and takes no
+// ticket (as adamw_kernel; sgd_kernel<.., true> differs).
 //
 // The {ratio, wd} table goes through LDS: each block copies the n_seg + 1 entries (8 bytes
 // each, at most 32 KiB) before its barrier.  Read straight from L2 the lookup would be two
 // dependent loads (cmap, then trust) in front of every quad's arithmetic; with the copy the
 // cmap load depends on nothing and is issued with the quad's p / g / momentum loads, and the
-// dependent read is an LDS access.
+// dependent read is an LDS access.  The fill runs whenever a.update is set, with or without
+// DLR, in front of the barrier the schedule protocol needs anyway.
 #include "kernels/bn_tail.h"
 #include "kernels/common.h"
+#include "kernels/flat_step.h"
 #include "kernels/launchers.h"
-#include "kernels/shadow.h"
 
 namespace ddp_amd {
 
@@ -175,14 +177,44 @@ __device__ __forceinline__ float lars_one(float v, float d, float* mb, const Sgd
   return fmaf(-a.lr, d, v);
 }
 
+// lars_kernel's rule for flat_stream: lars_one with the {ratio, wd} of the quad's tensor,
+// tab[min(cmap[i / 64], n_seg)] (n_seg: the null segment; the host sized cmap to ceil(n / 64))
+struct LarsRule {
+  float* mbuf;
+  SgdArgs a;
+  const short* cmap;
+  const float2* tab;
+  int n_seg;
+  // the tensor of flat element i: a load that depends on nothing - issue it with the quad's
+  // other loads, before entry() (the dependent LDS read) waits for it
+  __device__ __forceinline__ unsigned seg(long i) const { return (unsigned)(int)cmap[i >> 6]; }
+  __device__ __forceinline__ float2 entry(unsigned s) const { return tab[s < (unsigned)n_seg ? s : (unsigned)n_seg]; }
+  __device__ __forceinline__ float4 quad(long q, float4 v, float4 d) const {
+    const unsigned s = seg(q << 2);
+    float4 m = {0.f, 0.f, 0.f, 0.f};
+    if (a.momentum != 0.f) m = reinterpret_cast<const float4*>(mbuf)[q];
+    const float2 rw = entry(s);
+    v.x = lars_one(v.x, d.x, &m.x, a, rw);
+    v.y = lars_one(v.y, d.y, &m.y, a, rw);
+    v.z = lars_one(v.z, d.z, &m.z, a, rw);
+    v.w = lars_one(v.w, d.w, &m.w, a, rw);
+    if (a.momentum != 0.f) reinterpret_cast<float4*>(mbuf)[q] = m;
+    return v;
+  }
+  __device__ __forceinline__ float one(long i, float v, float d) const {
+    const unsigned s = seg(i);
+    float m = (a.momentum != 0.f) ? mbuf[i] : 0.f;
+    v = lars_one(v, d, &m, a, entry(s));
+    if (a.momentum != 0.f) mbuf[i] = m;
+    return v;
+  }
+};
+
 template <bool CLIP, bool DLR>
-__global__ __launch_bounds__(256) void lars_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                   float* __restrict__ mbuf, long n, SgdArgs a, ShadowSet sh,
-                                                   const short* __restrict__ cmap,
-                                                   const float4* __restrict__ trust, int n_seg,
-                                                   const float* __restrict__ gscale,
-                                                   const float* __restrict__ lr_table, int n_table,
-                                                   SchedState* __restrict__ sched) {
+__global__ __launch_bounds__(FLAT_THREADS) void lars_kernel(float* __restrict__ p, const float* __restrict__ g,
+    float* __restrict__ mbuf, long n, SgdArgs a, ShadowSet sh, const short* __restrict__ cmap,
+    const float4* __restrict__ trust, int n_seg, const float* __restrict__ gscale, const float* __restrict__ lr_table,
+    int n_table, SchedState* __restrict__ sched) {
   extern __shared__ float2 s_tab[];  // n_seg + 1 entries {ratio, wd}; the last is the null segment
   float gs = 1.f;
   if constexpr (CLIP) gs = gscale[0];
@@ -193,82 +225,24 @@ __global__ __launch_bounds__(256) void lars_kernel(float* __restrict__ p, const 
       s_tab[i] = make_float2(r.x, r.y);
     }
     if constexpr (DLR) {
-      t = __hip_atomic_load(&sched->t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      asm volatile("s_waitcnt vmcnt(0)" : "+v"(t) : : "memory");  // t is in a register from here on
-      t = __builtin_amdgcn_readfirstlane(t);
-      a.lr = lr_table[t < 0 ? 0 : (t < n_table ? t : n_table - 1)];
+      t = sched_read_t(sched);
+      a.lr = lr_table[sched_index(t, n_table)];
     }
     __syncthreads();  // the table is in LDS; DLR: every wave of the block has read t
-    if constexpr (DLR) {
-      if (threadIdx.x == 0)
-        ticket = __hip_atomic_fetch_add(&sched->ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if constexpr (DLR) ticket = sched_ticket(sched);
   }
-  const long n4 = n >> 2;
-  const long stride = (long)gridDim.x * blockDim.x;
-  for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < n4; q += stride) {
-    const long i = q << 2;
-    float4 v = reinterpret_cast<const float4*>(p)[q];
-    if (a.update) {
-      const unsigned s = (unsigned)(int)cmap[i >> 6];  // (the host sized cmap to ceil(n / 64))
-      float4 d = reinterpret_cast<const float4*>(g)[q];
-      float4 m = {0.f, 0.f, 0.f, 0.f};
-      if (a.momentum != 0.f) m = reinterpret_cast<const float4*>(mbuf)[q];
-      const float2 rw = s_tab[s < (unsigned)n_seg ? s : (unsigned)n_seg];
-      if constexpr (CLIP) { d.x *= gs; d.y *= gs; d.z *= gs; d.w *= gs; }
-      v.x = lars_one(v.x, d.x, &m.x, a, rw);
-      v.y = lars_one(v.y, d.y, &m.y, a, rw);
-      v.z = lars_one(v.z, d.z, &m.z, a, rw);
-      v.w = lars_one(v.w, d.w, &m.w, a, rw);
-      reinterpret_cast<float4*>(p)[q] = v;
-      if (a.momentum != 0.f) reinterpret_cast<float4*>(mbuf)[q] = m;
-    }
-    shadow_quad(sh, i, v);
-  }
-  // scalar tail
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-    const long i = (n4 << 2) + threadIdx.x;
-    float v = p[i];
-    if (a.update) {
-      const unsigned s = (unsigned)(int)cmap[i >> 6];
-      const float2 rw = s_tab[s < (unsigned)n_seg ? s : (unsigned)n_seg];
-      float m = (a.momentum != 0.f) ? mbuf[i] : 0.f;
-      float d = g[i];
-      if constexpr (CLIP) d *= gs;
-      v = lars_one(v, d, &m, a, rw);
-      p[i] = v;
-      if (a.momentum != 0.f) mbuf[i] = m;
-    }
-    shadow_one(sh, i, v);
-  }
-  if constexpr (DLR) {
-    if (threadIdx.x == 0 && ticket == (int)gridDim.x - 1) {  // the last arrival: every block has read t
-      __hip_atomic_store(&sched->t, t < 0x7fffffff ? t + 1 : t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&sched->lr_used, a.lr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&sched->ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-}
-
-template <bool CLIP, bool DLR>
-static void lars_launch(unsigned grid, hipStream_t s, float* p, const float* g, float* mbuf, long n,
-                        const SgdArgs& a, const ShadowSet& sh, const short* cmap, const float* trust, int n_seg,
-                        const float* gscale, const float* lr_table, int n_table, SchedState* sched) {
-  hipLaunchKernelGGL((lars_kernel<CLIP, DLR>), dim3(grid), dim3(256), (size_t)(n_seg + 1) * sizeof(float2), s, p, g,
-                     mbuf, n, a, sh, cmap, reinterpret_cast<const float4*>(trust), n_seg, gscale, lr_table, n_table,
-                     sched);
+  flat_stream<CLIP>(p, g, n, a.update, gs, sh, LarsRule{mbuf, a, cmap, s_tab, n_seg});
+  if constexpr (DLR) sched_finish(sched, t, ticket, a.lr);
 }
 
 void lars_step(float* p, const float* g, float* mbuf, long n, const SgdArgs& a, const ShadowSet& sh,
                const short* cmap, const float* trust, int n_seg, hipStream_t s, const float* gscale,
                const float* lr_table, int n_table, SchedState* sched) {
-  // 16-byte accesses need 16-byte-aligned buffers (torch allocations and flat views are)
-  const long blocks = ((n >> 2) + 255) / 256;
-  const unsigned grid = (unsigned)(blocks < 2048 ? (blocks > 0 ? blocks : 1) : 2048);
   const bool dlr = sched != nullptr && lr_table != nullptr && n_table > 0;
-  auto launch = gscale ? (dlr ? lars_launch<true, true> : lars_launch<true, false>)
-                       : (dlr ? lars_launch<false, true> : lars_launch<false, false>);
-  launch(grid, s, p, g, mbuf, n, a, sh, cmap, trust, n_seg, gscale, lr_table, n_table, sched);
+  auto kernel = gscale ? (dlr ? lars_kernel<true, true> : lars_kernel<true, false>)
+                       : (dlr ? lars_kernel<false, true> : lars_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, dim3(flat_grid(n)), dim3(FLAT_THREADS), (size_t)(n_seg + 1) * sizeof(float2), s, p, g, mbuf, n, a,
+                     sh, cmap, reinterpret_cast<const float4*>(trust), n_seg, gscale, lr_table, n_table, sched);
 }
 
 }  // namespace ddp_amd

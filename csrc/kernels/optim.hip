@@ -11,91 +11,58 @@
 // grad_reduce_kernel: fixed-order sum of split-K weight-gradient slabs into
 // gradient-bucket views, prescaled by 1/world_size (DDP averaging).
 #include "kernels/common.h"
+#include "kernels/flat_step.h"
 #include "kernels/launchers.h"
 #include "kernels/shadow.h"
 #include "kernels/slab_reduce.h"
 
 namespace ddp_amd {
 
-// 4 consecutive elements per thread (16-byte loads/stores); n4 = n / 4 quads, the
-// (n % 4) tail is handled by the first threads of block 0.
-// CLIP: the gradient is g[i] * gscale[0] (one fp32 multiply - the rounding of scaling the
-// gradient buffer in place, which is not rewritten); gscale[0] is the clip coefficient that
-// grad_sqnorm_kernel left in device memory, read once per thread, so a captured graph
-// replays with each step's own coefficient.
-// DLR: the learning rate is lr_table[min(t, n_table - 1)] with t = sched->t read from device
-// memory at run time (types.h SchedState), in place of a.lr - the float operations of sgd_one
-// are the same - and the launch itself advances t, so eager steps and replays of a captured
-// graph share one counter.  Every thread reads t once at entry (an agent-scope load: served
-// by L2, never by an L1 line of an earlier launch) and holds it in a register - the wait
-// consumes it - before the block's barrier; only then does thread 0 take a ticket (one
-// relaxed agent-scope add per block, the pattern of bn_tail.h last_arrival).  The ticket
-// publishes nothing but "this block has read t", so it needs no fence; the block that took
-// ticket gridDim.x - 1 knows every block has read t, writes t + 1 and lr_used and re-arms
-// the ticket.  The next launch sees t through the launch boundary, as it sees step_ctr.
-// The DLR = false builds run the code as it stood; they carry the three schedule arguments unused.
-// The ticket's return value is first used after the streaming loop, so thread 0's wave issues
-// its loads behind the atomic instead of waiting for it.
+// sgd_kernel's rule for flat_stream (flat_step.h): sgd_one; mbuf is touched only with momentum
+struct SgdRule {
+  float* mbuf;
+  SgdArgs a;
+  __device__ __forceinline__ float4 quad(long q, float4 v, float4 d) const {
+    float4 m = {0.f, 0.f, 0.f, 0.f};
+    if (a.momentum != 0.f) m = reinterpret_cast<const float4*>(mbuf)[q];
+    v.x = sgd_one(v.x, d.x, &m.x, a);
+    v.y = sgd_one(v.y, d.y, &m.y, a);
+    v.z = sgd_one(v.z, d.z, &m.z, a);
+    v.w = sgd_one(v.w, d.w, &m.w, a);
+    if (a.momentum != 0.f) reinterpret_cast<float4*>(mbuf)[q] = m;
+    return v;
+  }
+  __device__ __forceinline__ float one(long i, float v, float d) const {
+    float m = (a.momentum != 0.f) ? mbuf[i] : 0.f;
+    v = sgd_one(v, d, &m, a);
+    if (a.momentum != 0.f) mbuf[i] = m;
+    return v;
+  }
+};
+
+// Geometry, the CLIP multiply and the schedule protocol: flat_step.h.  DLR: the learning rate is
+// lr_table[min(t, n_table - 1)] in place of a.lr - the float operations of sgd_one are the same.
+// The DLR = false builds carry the three schedule arguments unused.
+// Unlike adamw_kernel and lars_kernel, the DLR build reads t, takes a ticket and advances t on
+// a shadows-only launch (a.update == 0) too: to this kernel every launch is a step of the
+// schedule.  FusedSGD issues no such launch; the binding allows it, and a test pins it.
 template <bool CLIP, bool DLR>
-__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                  float* __restrict__ mbuf, long n, SgdArgs a,
-                                                  ShadowSet sh, int* __restrict__ step_ctr,
-                                                  const float* __restrict__ gscale,
-                                                  const float* __restrict__ lr_table, int n_table,
-                                                  SchedState* __restrict__ sched) {
+__global__ __launch_bounds__(FLAT_THREADS) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g,
+    float* __restrict__ mbuf, long n, SgdArgs a, ShadowSet sh, int* __restrict__ step_ctr,
+    const float* __restrict__ gscale, const float* __restrict__ lr_table, int n_table,
+    SchedState* __restrict__ sched) {
   DDP_STAMP(STAMP_K_SGD, 0);
   float gs = 1.f;
   if constexpr (CLIP) gs = gscale[0];
   int t = 0, ticket = -1;
   if constexpr (DLR) {
-    t = __hip_atomic_load(&sched->t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(t) : : "memory");  // t is in a register from here on
-    t = __builtin_amdgcn_readfirstlane(t);
-    a.lr = lr_table[t < 0 ? 0 : (t < n_table ? t : n_table - 1)];
+    t = sched_read_t(sched);
+    a.lr = lr_table[sched_index(t, n_table)];
     __syncthreads();  // every wave of the block has read t
-    if (threadIdx.x == 0)
-      ticket = __hip_atomic_fetch_add(&sched->ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    ticket = sched_ticket(sched);
   }
-  const long n4 = n >> 2;
-  const long stride = (long)gridDim.x * blockDim.x;
-  for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < n4; q += stride) {
-    const long i = q << 2;
-    float4 v = reinterpret_cast<const float4*>(p)[q];
-    if (a.update) {
-      float4 d = reinterpret_cast<const float4*>(g)[q];
-      if constexpr (CLIP) { d.x *= gs; d.y *= gs; d.z *= gs; d.w *= gs; }
-      float4 m = {0.f, 0.f, 0.f, 0.f};
-      if (a.momentum != 0.f) m = reinterpret_cast<const float4*>(mbuf)[q];
-      v.x = sgd_one(v.x, d.x, &m.x, a);
-      v.y = sgd_one(v.y, d.y, &m.y, a);
-      v.z = sgd_one(v.z, d.z, &m.z, a);
-      v.w = sgd_one(v.w, d.w, &m.w, a);
-      reinterpret_cast<float4*>(p)[q] = v;
-      if (a.momentum != 0.f) reinterpret_cast<float4*>(mbuf)[q] = m;
-    }
-    shadow_quad(sh, i, v);
-  }
-  // scalar tail
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-    const long i = (n4 << 2) + threadIdx.x;
-    float v = p[i];
-    if (a.update) {
-      float m = (a.momentum != 0.f) ? mbuf[i] : 0.f;
-      float d = g[i];
-      if constexpr (CLIP) d *= gs;
-      v = sgd_one(v, d, &m, a);
-      p[i] = v;
-      if (a.momentum != 0.f) mbuf[i] = m;
-    }
-    shadow_one(sh, i, v);
-  }
-  if constexpr (DLR) {
-    if (threadIdx.x == 0 && ticket == (int)gridDim.x - 1) {  // the last arrival: every block has read t
-      __hip_atomic_store(&sched->t, t < 0x7fffffff ? t + 1 : t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&sched->lr_used, a.lr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&sched->ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  flat_stream<CLIP>(p, g, n, a.update, gs, sh, SgdRule{mbuf, a});
+  if constexpr (DLR) sched_finish(sched, t, ticket, a.lr);
   if (step_ctr && blockIdx.x == 0 && threadIdx.x == 0) step_ctr[0] += 1;
   DDP_STAMP(STAMP_K_SGD, 1);
 }
@@ -122,24 +89,14 @@ __global__ void scale_copy_kernel(float* __restrict__ dst, const float* __restri
     dst[i] = src[i] * scale;
 }
 
-template <bool CLIP, bool DLR>
-static void sgd_launch(unsigned grid, hipStream_t s, float* p, const float* g, float* mbuf, long n,
-                       const SgdArgs& a, const ShadowSet& sh, int* step_ctr, const float* gscale,
-                       const float* lr_table, int n_table, SchedState* sched) {
-  hipLaunchKernelGGL((sgd_kernel<CLIP, DLR>), dim3(grid), dim3(256), 0, s, p, g, mbuf, n, a, sh, step_ctr, gscale,
-                     lr_table, n_table, sched);
-}
-
 void sgd_step(float* p, const float* g, float* mbuf, long n, const SgdArgs& a, const ShadowSet& sh,
               int* step_ctr, hipStream_t s, const float* gscale, const float* lr_table, int n_table,
               SchedState* sched) {
-  // 16-byte accesses need 16-byte-aligned buffers (torch allocations and flat views are)
-  const long blocks = ((n >> 2) + 255) / 256;
-  const unsigned grid = (unsigned)(blocks < 2048 ? (blocks > 0 ? blocks : 1) : 2048);
   const bool dlr = sched != nullptr && lr_table != nullptr && n_table > 0;
-  auto launch = gscale ? (dlr ? sgd_launch<true, true> : sgd_launch<true, false>)
-                       : (dlr ? sgd_launch<false, true> : sgd_launch<false, false>);
-  launch(grid, s, p, g, mbuf, n, a, sh, step_ctr, gscale, lr_table, n_table, sched);
+  auto kernel = gscale ? (dlr ? sgd_kernel<true, true> : sgd_kernel<true, false>)
+                       : (dlr ? sgd_kernel<false, true> : sgd_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, dim3(flat_grid(n)), dim3(FLAT_THREADS), 0, s, p, g, mbuf, n, a, sh, step_ctr, gscale,
+                     lr_table, n_table, sched);
 }
 
 // empty kernel: the per-launch floor (dispatch + drain + boundary) for kernel benches

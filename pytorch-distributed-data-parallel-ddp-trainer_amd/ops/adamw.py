@@ -199,26 +199,15 @@ class FusedAdamW(FlatOptimizer):
             v = _to_reference_layout(self.model, self.flat, self.exp_avg_sq)
             for i, n in enumerate(self._reg_names):
                 state[i] = {"step": torch.tensor(step, dtype=torch.float32), "exp_avg": m[n], "exp_avg_sq": v[n]}
-        d = dict(self.param_groups[0])
-        if self.lr_schedule is not None:
-            d["lr"] = self.current_lr()
-        d["params"] = list(range(len(self._reg_names)))
-        return {"state": state, "param_groups": [d]}
+        return {"state": state, "param_groups": [self._group_to_save(dict(self.param_groups[0]))]}
 
     def load_state_dict(self, sd):
-        groups = sd["param_groups"]
-        if len(groups) != 1 or len(groups[0]["params"]) != len(self._reg_names):
-            raise ValueError("optimizer state_dict does not match this model")
-        if groups[0].get("amsgrad"):
+        saved = self._saved_group(sd)
+        if saved.get("amsgrad"):
             raise ValueError("FusedAdamW does not support amsgrad=True")
         g = self.param_groups[0]
-        for k in g:
-            if k == "lr" and self.lr_schedule is not None:
-                # a checkpoint's lr is a point of the schedule: the base is the constructor's
-                self.loaded_lr = groups[0].get("lr")  # (kept so a resume can check its step index)
-                continue
-            if k in groups[0]:
-                g[k] = tuple(groups[0][k]) if k == "betas" else groups[0][k]
+        self._load_group(saved, list(g))
+        g["betas"] = tuple(g["betas"])
         self.hyper_changed()
         st = sd.get("state", {})
         if st:

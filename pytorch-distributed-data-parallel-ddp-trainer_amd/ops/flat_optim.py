@@ -1,8 +1,9 @@
-"""What the flat-buffer optimizers (``FusedSGD``, ``FusedAdamW``) share.
+"""What the flat-buffer optimizers (``FusedSGD``, ``FusedAdamW``, ``FusedLARS``) share.
 
-Both update the model's one flat fp32 parameter buffer in one HIP kernel that also refreshes
-the shadow copies the MFMA kernels read, and both keep their per-step scalars in device
-memory so that a captured step graph replays each step with its own values:
+Each updates the model's one flat fp32 parameter buffer in one HIP kernel - a rule on the
+streaming pass of csrc/kernels/flat_step.h - that also refreshes the shadow copies the MFMA
+kernels read, and each keeps its per-step scalars in device memory so that a captured step
+graph replays each step with its own values:
 
 * the clip workspace - ``grad_sqnorm_kernel`` (csrc/kernels/grad_norm.hip) leaves the global
   norm of the flat gradient and the coefficient ``min(1, max_norm / (norm + 1e-6))`` in device
@@ -12,7 +13,9 @@ memory so that a captured step graph replays each step with its own values:
   ``table[min(t, n - 1)]`` and advances ``t`` inside the same launch.  On the CPU the same table
   is indexed by a host counter;
 * the conversion between the flat buffers and the per-parameter layouts of a reference
-  (``torch.optim``) state dict.
+  (``torch.optim``) state dict, and the one rule for ``lr`` in it: with a schedule the saved
+  ``lr`` is the rate the next step will use (as a torch scheduler leaves it) and a loaded one is
+  a point of the schedule, kept in ``loaded_lr`` and not applied.
 """
 from __future__ import annotations
 
@@ -156,6 +159,32 @@ class FlatOptimizer:
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("set_schedule_step inside a graph capture")
             self._sched_ws[1].copy_(torch.tensor([k, 0, 0, 0], dtype=torch.int32))
+
+    # ------------------------------------------------------------------ state dict
+    def _group_to_save(self, d: dict) -> dict:
+        """``d`` - the group's hyper-parameters under the reference's keys, in its order - as the
+        param group of a state dict."""
+        if self.lr_schedule is not None:
+            d["lr"] = self.current_lr()
+        d["params"] = list(range(len(self._reg_names)))
+        return d
+
+    def _saved_group(self, sd) -> dict:
+        """The one param group of a state dict for this model."""
+        groups = sd["param_groups"]
+        if len(groups) != 1 or len(groups[0]["params"]) != len(self._reg_names):
+            raise ValueError("optimizer state_dict does not match this model")
+        return groups[0]
+
+    def _load_group(self, saved: dict, keys):
+        """Take the hyper-parameters ``keys`` that ``saved`` has (missing ones keep their values)."""
+        g = self.param_groups[0]
+        for k in keys:
+            if k == "lr" and self.lr_schedule is not None:
+                # a checkpoint's lr is a point of the schedule: the base is the constructor's
+                self.loaded_lr = saved.get("lr")  # (kept so a resume can check its step index)
+            elif k in saved:
+                g[k] = saved[k]
 
 
 def _owner(model, name):

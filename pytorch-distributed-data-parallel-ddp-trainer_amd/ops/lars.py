@@ -35,8 +35,7 @@ import numpy as np
 import torch
 
 from . import kernel_bounds as kb
-from .flat_optim import FlatOptimizer, _from_reference_layout, _to_reference_layout
-from .sgd import _DEFAULTS
+from .sgd import _DEFAULTS, FusedSGD
 
 ITEM, CHUNK, MAX_SEGS = kb.LARS_ITEM, kb.LARS_CHUNK, 4095  # csrc/kernels/launchers.h
 _EXTRA = ("trust_coef", "eps", "exclude")
@@ -68,25 +67,25 @@ def lars_layout(begins, numels, n: int, wds, adapts):
     return torch.from_numpy(segs), torch.from_numpy(items), torch.from_numpy(cmap)
 
 
-class FusedLARS(FlatOptimizer):
+class FusedLARS(FusedSGD):
+    """``FusedSGD``'s momentum state, state-dict format and momentum step; its own gradient rule
+    (per-tensor decay and trust ratio) and kernels."""
+
+    _group_keys = (*_DEFAULTS, *_EXTRA)
+
     def __init__(self, model: torch.nn.Module, lr: float = 1e-3, momentum: float = 0.9, dampening: float = 0,
                  weight_decay: float = 0, nesterov: bool = False, maximize: bool = False,
                  trust_coef: float = 1e-3, eps: float = 1e-8, exclude="1d",
                  max_grad_norm: float | None = None, lr_schedule=None):
-        if nesterov and (momentum <= 0 or dampening != 0):
-            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         if not trust_coef > 0:
             raise ValueError("trust_coef must be positive")
         if eps < 0 or weight_decay < 0:
             raise ValueError("eps and weight_decay must be >= 0")
         if not (exclude is None or exclude == "1d" or callable(exclude)):
             raise ValueError("exclude must be '1d', None or a callable (name, shape) -> bool")
-        self._init_flat(model, max_grad_norm, lr_schedule)
-        g = dict(_DEFAULTS)
-        g.update(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
-                 nesterov=nesterov, maximize=maximize, trust_coef=trust_coef, eps=eps, exclude=exclude)
-        self.param_groups = [g]
-        self.momentum_buffer: torch.Tensor | None = None
+        super().__init__(model, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                         nesterov=nesterov, maximize=maximize, max_grad_norm=max_grad_norm, lr_schedule=lr_schedule)
+        self.param_groups[0].update(trust_coef=trust_coef, eps=eps, exclude=exclude)
         self._excluded_wd = 0.0   # decay of the excluded tensors (0 by definition; the SGD-anchor test forces it)
         self._ws = None           # GPU: (plan, partials, ticket, sums, trust), allocated by the first step
         self._host_stats = None   # CPU: float32 [n_seg, 4] {ratio, wd, wn, gn} of the last step
@@ -135,34 +134,21 @@ class FusedLARS(FlatOptimizer):
         if self._ws is not None:
             self._ws[0][0].copy_(self.layout()[0])
 
-    # ------------------------------------------------------------------ API
-    @torch.no_grad()
-    def step(self):
+    # ------------------------------------------------------------------ the step
+    def _step_native(self, C, first: bool):
         g = self.param_groups[0]
         fs = self.flat
-        self._prepare_grads()
-        first = self.momentum_buffer is None
-        if g["momentum"] != 0 and first:
-            self.momentum_buffer = torch.zeros_like(fs.params)
-        if fs.params.is_cuda:
-            from .. import native
+        shadows = self._all_shadows()
+        plan, partials, ticket, sums, trust = self._workspace(C)
+        gscale = self._gscale(C)  # (grad_sqnorm first: seg_sqnorm reads its coefficient)
+        sched = self._sched_workspace() if self.lr_schedule is not None else None
+        C.seg_sqnorm(fs.params, fs.grads, plan, partials, ticket, sums, trust, g["trust_coef"], g["eps"], gscale)
+        C.lars(fs.params, fs.grads, self.momentum_buffer, g["lr"], g["momentum"], g["dampening"],
+               g["nesterov"], g["maximize"], first, True, shadows, plan, trust, gscale, sched)
 
-            shadows = self._all_shadows()
-            C = native.require()
-            plan, partials, ticket, sums, trust = self._workspace(C)
-            gscale = self._gscale(C)  # (grad_sqnorm first: seg_sqnorm reads its coefficient)
-            sched = self._sched_workspace() if self.lr_schedule is not None else None
-            C.seg_sqnorm(fs.params, fs.grads, plan, partials, ticket, sums, trust, g["trust_coef"], g["eps"], gscale)
-            C.lars(fs.params, fs.grads, self.momentum_buffer, g["lr"], g["momentum"], g["dampening"],
-                   g["nesterov"], g["maximize"], first, True, shadows, plan, trust, gscale, sched)
-            fs.mark_bf16_fresh()
-        else:
-            self._step_torch(first)
-        self.steps += 1
-
-    def _step_torch(self, first: bool):
+    def _grad_torch(self) -> torch.Tensor:
         """The kernels' rule with torch ops: per tensor the norms (summed in float64, rounded
-        once) and the fp32 ratio, then the element sequence of lars.hip over the flat buffers."""
+        once) and the fp32 ratio, then lars.hip's element sequence up to the momentum lines."""
         g = self.param_groups[0]
         fs = self.flat
         p, raw = fs.params, fs.grads
@@ -184,18 +170,7 @@ class FusedLARS(FlatOptimizer):
                 di.add_(w, alpha=float(np.float32(wds[s])))
             di.mul_(float(ratio))
         self._host_stats = stats
-        if g["momentum"] != 0:
-            buf = self.momentum_buffer
-            if first:
-                buf.copy_(d)
-            else:
-                buf.mul_(g["momentum"]).add_(d, alpha=1 - g["dampening"])
-            d = d.add(buf, alpha=g["momentum"]) if g["nesterov"] else buf
-        lr = g["lr"]
-        if self.lr_schedule is not None:
-            lr = self.lr_schedule.lr_at(self._sched_t)
-            self._sched_t += 1
-        p.add_(d, alpha=-lr)
+        return d
 
     def trust_stats(self) -> dict | None:
         """Per parameter name ``{"w_norm", "g_norm", "ratio", "adapted"}`` of the last step; on the
@@ -211,58 +186,12 @@ class FusedLARS(FlatOptimizer):
                     "adapted": bool(adapts[s])} for s, n in enumerate(self.flat.names)}
 
     # ------------------------------------------------------------------ state
-    def state_buffers(self) -> dict:
-        """The optimizer state as named flat tensors (``None``: not created yet) - what a
-        resume broadcasts and ``--verify_replicas`` hashes."""
-        return {"momentum_buffer": self.momentum_buffer}
-
-    def set_state_buffer(self, name: str, buf: torch.Tensor):
-        assert name == "momentum_buffer"
-        self.momentum_buffer = buf
-
-    def state_dict(self):
-        state = {}
-        if self.momentum_buffer is not None:
-            ref = _to_reference_layout(self.model, self.flat, self.momentum_buffer)
-            for i, n in enumerate(self._reg_names):
-                state[i] = {"momentum_buffer": ref[n]}
-        g = self.param_groups[0]
-        d = {k: g[k] for k in (*_DEFAULTS, *_EXTRA)}
+    def _group_values(self) -> dict:
+        d = super()._group_values()
         if callable(d["exclude"]):
             d["exclude"] = "callable"  # (a function does not belong in a checkpoint: the constructor's is kept)
-        if self.lr_schedule is not None:
-            d["lr"] = self.current_lr()
-        d["params"] = list(range(len(self._reg_names)))
-        return {"state": state, "param_groups": [d]}
+        return d
 
-    def load_state_dict(self, sd):
-        groups = sd["param_groups"]
-        if len(groups) != 1 or len(groups[0]["params"]) != len(self._reg_names):
-            raise ValueError("optimizer state_dict does not match this model")
-        g = self.param_groups[0]
-        for k in (*_DEFAULTS, *_EXTRA):
-            if k == "lr" and self.lr_schedule is not None:
-                # a checkpoint's lr is a point of the schedule: the base is the constructor's
-                self.loaded_lr = groups[0].get("lr")  # (kept so a resume can check its step index)
-                continue
-            if k == "exclude" and groups[0].get(k) not in (None, "1d"):
-                continue
-            if k in groups[0]:
-                g[k] = groups[0][k]
+    def _load_group(self, saved: dict, keys):
+        super()._load_group(saved, [k for k in keys if k != "exclude" or saved.get(k) in (None, "1d")])
         self.hyper_changed()
-        st = sd.get("state", {})
-        if st:
-            buf = torch.zeros_like(self.flat.params)
-            ref = {self._reg_names[int(i)]: v["momentum_buffer"] for i, v in st.items()
-                   if "momentum_buffer" in v}
-            _from_reference_layout(self.model, self.flat, ref, buf)
-            self.momentum_buffer = buf
-            self.steps = max(self.steps, 1)  # a loaded buffer: the next step is a regular update
-        else:
-            self.momentum_buffer = None
-            self.steps = 0
-
-    def mark_started(self):
-        """A momentum buffer arrived from elsewhere (resume broadcast): treat as started."""
-        if self.momentum_buffer is not None:
-            self.steps = max(self.steps, 1)

@@ -41,6 +41,11 @@ _DEFAULTS = dict(lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=Fals
 
 
 class FusedSGD(FlatOptimizer):
+    """Also the base of ``FusedLARS`` (ops/lars.py), which keeps the momentum state, its state
+    dict and the momentum half of the CPU step, and replaces the gradient rule and the launch."""
+
+    _group_keys = tuple(_DEFAULTS)  # the param group's keys in a state dict, in order
+
     def __init__(self, model: torch.nn.Module, lr: float = 1e-3, momentum: float = 0,
                  dampening: float = 0, weight_decay: float = 0, nesterov: bool = False,
                  maximize: bool = False, max_grad_norm: float | None = None, lr_schedule=None):
@@ -56,27 +61,30 @@ class FusedSGD(FlatOptimizer):
     # ------------------------------------------------------------------ API
     @torch.no_grad()
     def step(self):
-        g = self.param_groups[0]
         fs = self.flat
         self._prepare_grads()
         first = self.momentum_buffer is None
-        if g["momentum"] != 0 and first:
+        if self.param_groups[0]["momentum"] != 0 and first:
             self.momentum_buffer = torch.zeros_like(fs.params)
         if fs.params.is_cuda:
             from .. import native
 
-            shadows = self._all_shadows()  # incl. the model's bf16 weight copy, refreshed in the same pass
-            C = native.require()
-            gscale = self._gscale(C)
-            # with a schedule every step, eager or captured, runs the DLR build: one device counter
-            sched = self._sched_workspace() if self.lr_schedule is not None else None
-            C.sgd(fs.params, fs.grads, self.momentum_buffer, g["lr"], g["momentum"],
-                  g["dampening"], g["weight_decay"], g["nesterov"], g["maximize"],
-                  first, True, shadows, gscale, sched)
+            self._step_native(native.require(), first)
             fs.mark_bf16_fresh()
         else:
             self._step_torch(first)
         self.steps += 1
+
+    def _step_native(self, C, first: bool):
+        g = self.param_groups[0]
+        fs = self.flat
+        shadows = self._all_shadows()  # incl. the model's bf16 weight copy, refreshed in the same pass
+        gscale = self._gscale(C)
+        # with a schedule every step, eager or captured, runs the DLR build: one device counter
+        sched = self._sched_workspace() if self.lr_schedule is not None else None
+        C.sgd(fs.params, fs.grads, self.momentum_buffer, g["lr"], g["momentum"],
+              g["dampening"], g["weight_decay"], g["nesterov"], g["maximize"],
+              first, True, shadows, gscale, sched)
 
     def state_buffers(self) -> dict:
         """The optimizer state as named flat tensors (``None``: not created yet) - what a
@@ -87,7 +95,8 @@ class FusedSGD(FlatOptimizer):
         assert name == "momentum_buffer"
         self.momentum_buffer = buf
 
-    def _step_torch(self, first: bool):
+    def _grad_torch(self) -> torch.Tensor:
+        """The (clipped, with ``maximize`` negated) gradient plus the weight decay, a new tensor."""
         g = self.param_groups[0]
         p, d = self.flat.params, self.flat.grads
         if self.max_grad_norm is not None:
@@ -95,6 +104,11 @@ class FusedSGD(FlatOptimizer):
         d = -d if g["maximize"] else d.clone()
         if g["weight_decay"] != 0:
             d = d.add(p, alpha=g["weight_decay"])
+        return d
+
+    def _step_torch(self, first: bool):
+        g = self.param_groups[0]
+        d = self._grad_torch()
         if g["momentum"] != 0:
             buf = self.momentum_buffer
             if first:
@@ -106,35 +120,23 @@ class FusedSGD(FlatOptimizer):
         if self.lr_schedule is not None:
             lr = self.lr_schedule.lr_at(self._sched_t)
             self._sched_t += 1
-        p.add_(d, alpha=-lr)
+        self.flat.params.add_(d, alpha=-lr)
 
     # ------------------------------------------------------------------ state
+    def _group_values(self) -> dict:
+        g = self.param_groups[0]
+        return {k: g[k] for k in self._group_keys}
+
     def state_dict(self):
         state = {}
         if self.momentum_buffer is not None:
             ref = _to_reference_layout(self.model, self.flat, self.momentum_buffer)
             for i, n in enumerate(self._reg_names):
                 state[i] = {"momentum_buffer": ref[n]}
-        groups = []
-        for g in self.param_groups:
-            d = {k: g[k] for k in _DEFAULTS}
-            if self.lr_schedule is not None:
-                d["lr"] = self.current_lr()
-            d["params"] = list(range(len(self._reg_names)))
-            groups.append(d)
-        return {"state": state, "param_groups": groups}
+        return {"state": state, "param_groups": [self._group_to_save(self._group_values())]}
 
     def load_state_dict(self, sd):
-        groups = sd["param_groups"]
-        if len(groups) != 1 or len(groups[0]["params"]) != len(self._reg_names):
-            raise ValueError("optimizer state_dict does not match this model")
-        for k in _DEFAULTS:
-            if k == "lr" and self.lr_schedule is not None:
-                # a checkpoint's lr is a point of the schedule: the base is the constructor's
-                self.loaded_lr = groups[0].get("lr")  # (kept so a resume can check its step index)
-                continue
-            if k in groups[0]:
-                self.param_groups[0][k] = groups[0][k]
+        self._load_group(self._saved_group(sd), self._group_keys)
         st = sd.get("state", {})
         if st:
             buf = torch.zeros_like(self.flat.params)

@@ -128,6 +128,35 @@ def test_counter_is_exact_over_300_launches(C, n):
     assert torch.equal(p.cpu(), torch.full((n,), -sum(rates)))  # each launch used its own entry, once
 
 
+@pytest.mark.parametrize("n", [1027, 1031])
+def test_shadows_only_launch_still_advances_the_sgd_schedule(C, n):
+    """sgd_kernel<.., true> with update = False (the binding allows it; FusedSGD never issues it):
+    parameters and momentum untouched, the shadow written, and - unlike adamw_kernel and
+    lars_kernel, to which such a launch is no optimizer step - t moves from k to k + 1 with the
+    ticket re-armed.  n = 1027: 256 quads, one full block, plus a 3-element tail; n = 1031: 257
+    quads, so two blocks (the ticket counts two arrivals), plus a 3-element tail."""
+    assert ((n >> 2) + 255) // 256 == (1 if n == 1027 else 2) and n % 4 == 3
+    gen = torch.Generator().manual_seed(5)
+    p0, m0 = torch.randn(n, generator=gen), torch.randn(n, generator=gen)
+    pb, p = guarded(n, torch.float32)
+    mb, m = guarded(n, torch.float32)
+    sb, sh = guarded(n, torch.bfloat16)
+    p.copy_(p0)
+    m.copy_(m0)
+    g = torch.randn(n, generator=gen).to(dev)
+    sc = Sched(RATES)
+    for k in range(2):
+        sh.fill_(SENT)
+        C.sgd(p, g, m, 999.0, 0.9, 0.0, 1e-2, False, False, False, False, [(0, n, sh, 1, 0, 0, 0)], None, sc.arg())
+        torch.cuda.synchronize()
+        assert torch.equal(p.cpu(), p0) and torch.equal(m.cpu(), m0), "a shadows-only launch updates nothing"
+        assert torch.equal(sh.cpu(), p0.to(torch.bfloat16))
+        t, ticket, lr_used = sc.read()
+        assert (t, ticket) == (k + 1, 0)
+        assert lr_used == torch.tensor(RATES, dtype=torch.float32)[k].item()
+    assert guards_intact(pb, n) and guards_intact(mb, n) and guards_intact(sb, n)
+
+
 def test_binding_checks_the_schedule_operands(C):
     p, g = torch.zeros(8, device=dev), torch.zeros(8, device=dev)
     table = torch.ones(3, device=dev)
