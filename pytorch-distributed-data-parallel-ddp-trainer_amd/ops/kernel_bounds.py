@@ -294,6 +294,7 @@ def sqnorm_bound(n, sumsq64):
 
 # ------------------------------------------------------------ LARS: per-tensor norms, trust ratio
 LARS_ITEM, LARS_CHUNK = 4096, 64  # csrc/kernels/launchers.h
+LARS_MAX_BLOCKS, LARS_MAX_SEGS = 2048, 4095  # seg_sqnorm_kernel's grid cap; tensors per plan
 
 
 def lars_items(numel):
@@ -301,23 +302,35 @@ def lars_items(numel):
     return -(-int(numel) // LARS_ITEM)
 
 
+def replay_item_partials(rows32):
+    """[items][LARS_ITEM] float32 rows (elements at or past an item's len as +0.0f) -> [items]
+    partials, steps 1 to 4 of seg_sqnorm_kernel's documented order (csrc/kernels/lars.hip,
+    header): per item the 256 threads' folded squares, the wave trees and the block sum."""
+    rows32 = np.asarray(rows32, dtype=np.float32).reshape(-1, LARS_ITEM)
+    # fmaf(x, x, +0.0f) is the product rounded once: the float32 multiply (and +0.0f for x = -0.0f)
+    sq = (rows32 * rows32).reshape(rows32.shape[0], 4, GN_THREADS, 4)  # [item][u][thread][c]
+    s = ((sq[..., 0] + sq[..., 1]).astype(np.float32) + (sq[..., 2] + sq[..., 3]).astype(np.float32)).astype(np.float32)
+    th = ((s[:, 0] + s[:, 1]).astype(np.float32) + (s[:, 2] + s[:, 3]).astype(np.float32)).astype(np.float32)
+    return _block_sum(th)
+
+
+def replay_seg_finish(part32):
+    """One tensor's item partials, in item order -> its sum, step 5 of the same order: lane j's
+    sequential sum of the partials j, j + 64, ... from +0.0f, then one more wave tree."""
+    lanes = np.zeros(64, dtype=np.float32)
+    for k, p in enumerate(np.asarray(part32, dtype=np.float32).reshape(-1)):  # lane k % 64, in item order
+        lanes[k % 64] = np.float32(lanes[k % 64] + p)
+    return np.float32(_wave_tree(lanes.reshape(1, 64))[0])
+
+
 def replay_seg_sqnorm(x32):
     """The float32 sum of squares of one tensor's elements x32 in seg_sqnorm_kernel's documented
-    order (csrc/kernels/lars.hip, header): per item the 256 threads' folded squares, the wave
-    trees and the block sum; then lane j's sequential sum of the item partials j, j + 64, ...
-    and one more wave tree."""
+    order: replay_item_partials over its items, then replay_seg_finish."""
     x32 = np.asarray(x32, dtype=np.float32).reshape(-1)
     k_n = lars_items(x32.size)
     buf = np.zeros(max(k_n, 1) * LARS_ITEM, dtype=np.float32)  # elements past len count as +0.0f
     buf[:x32.size] = x32
-    sq = _fma32(buf, np.zeros_like(buf)).reshape(max(k_n, 1), 4, GN_THREADS, 4)  # [item][u][thread][c]
-    s = ((sq[..., 0] + sq[..., 1]).astype(np.float32) + (sq[..., 2] + sq[..., 3]).astype(np.float32)).astype(np.float32)
-    th = ((s[:, 0] + s[:, 1]).astype(np.float32) + (s[:, 2] + s[:, 3]).astype(np.float32)).astype(np.float32)
-    part = _block_sum(th)[:k_n]  # [item]
-    lanes = np.zeros(64, dtype=np.float32)
-    for k in range(k_n):  # lane k % 64 adds its partials in item order
-        lanes[k % 64] = np.float32(lanes[k % 64] + part[k])
-    return np.float32(_wave_tree(lanes.reshape(1, 64))[0])
+    return replay_seg_finish(replay_item_partials(buf)[:k_n])
 
 
 def seg_sqnorm_chain(numel):

@@ -37,7 +37,7 @@ import torch
 from . import kernel_bounds as kb
 from .sgd import _DEFAULTS, FusedSGD
 
-ITEM, CHUNK, MAX_SEGS = kb.LARS_ITEM, kb.LARS_CHUNK, 4095  # csrc/kernels/launchers.h
+ITEM, CHUNK, MAX_SEGS = kb.LARS_ITEM, kb.LARS_CHUNK, kb.LARS_MAX_SEGS  # csrc/kernels/launchers.h
 _EXTRA = ("trust_coef", "eps", "exclude")
 
 
