@@ -400,6 +400,15 @@ void seg_sqnorm(const float* w, const float* g, long n, const LarsItem* items, i
 void lars_step(float* p, const float* g, float* mbuf, long n, const SgdArgs& a, const ShadowSet& sh,
                const short* cmap, const float* trust, int n_seg, hipStream_t s, const float* gscale = nullptr,
                const float* lr_table = nullptr, int n_table = 0, SchedState* sched = nullptr);
+// ---- weight EMA (ema.hip) --------------------------------------------------------------
+// One update e' = fma(om, p - e, e) over the flat fp32 EMA buffer e and the live parameters p.
+// sched == nullptr: the constant-decay build, om by value, num_updates[0] += 1 (one int in
+// device memory).  sched != nullptr: the warm-up build, om = table[min(sched->t, n_table - 1)]
+// read at run time; the launch advances sched->t (the EMA's own SchedState, its update count).
+void ema_step(float* e, const float* p, long n, float om, int* num_updates, hipStream_t s,
+              const float* table = nullptr, int n_table = 0, SchedState* sched = nullptr);
+// Exchange p and e (n elements each, not overlapping) and refresh the shadows of the new p.
+void ema_swap(float* p, float* e, long n, const ShadowSet& sh, hipStream_t s);
 // ---- global gradient norm / clip coefficient (grad_norm.hip) --------------------------
 constexpr int GN_THREADS = 256, GN_QUADS = 4, GN_MAX_BLOCKS = 1024;
 struct ClipStats {

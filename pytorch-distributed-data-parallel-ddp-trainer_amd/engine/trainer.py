@@ -35,7 +35,7 @@ from ..models.layers import buffer_space, flat_space
 from ..ops import CrossEntropyLoss, FusedAdamW, FusedLARS, FusedSGD
 from ..parallel import DistributedDataParallel as DDP
 from ..parallel import cleanup, local_rank, native_comm, setup
-from ..utils.checkpoint import resume, save_checkpoint
+from ..utils.checkpoint import resume, resume_ema, save_checkpoint
 
 
 @dataclasses.dataclass
@@ -92,6 +92,9 @@ class TrainOptions:
     trust_coef: float = 1e-3          # lars: the trust ratio's coefficient
     lars_eps: float = 1e-8            # lars: the trust ratio denominator's epsilon
     lars_exclude: str = "1d"          # lars: 1d (BatchNorm scales, biases: ratio 1, no decay) | none
+    ema_decay: float = 0.0            # weight EMA updated by every optimizer step (0: off; module/CPU path)
+    ema_warmup: bool = False          # decay_k = min(ema_decay, (1 + k) / (10 + k)) for update k
+    eval_ema: bool = False            # every evaluation also evaluates the averaged weights
 
 
 def validate_options(opts: TrainOptions):
@@ -122,6 +125,10 @@ def validate_options(opts: TrainOptions):
             raise ValueError("--trust_coef must be positive and --lars_eps >= 0")
         if opts.lars_exclude not in ("1d", "none"):
             raise ValueError(f"--lars_exclude must be 1d or none, got {opts.lars_exclude!r}")
+    if not 0.0 <= opts.ema_decay < 1.0:
+        raise ValueError("--ema_decay must lie in [0, 1) (0 = off)")
+    if (opts.eval_ema or opts.ema_warmup) and not opts.ema_decay:
+        raise ValueError("--eval_ema / --ema_warmup need a weight EMA: set --ema_decay D")
     if opts.optimizer == "adamw" and opts.momentum != 0:
         raise ValueError("--momentum is SGD's; --optimizer adamw takes --beta1 / --beta2 / --adam_eps")
     if (opts.device or "").lower() == "gpu":  # the fused engine is certain: refuse before any process starts
@@ -141,6 +148,10 @@ def check_fused_engine_options(opts: TrainOptions, fused: bool):
         raise ValueError("--lr_schedule / --warmup_steps need the module path (--engine module) or the CPU "
                          "path; the fused engine bakes the learning rate into its kernels' arguments and "
                          "into its captured step graphs")
+    if fused and opts.ema_decay:
+        raise ValueError("--ema_decay needs the module path (--engine module) or the CPU path; the fused "
+                         "engine applies SGD inside the kernels that finish each gradient and its captured "
+                         "step graphs hold no averaging pass")
     if fused and opts.optimizer == "lars":
         raise ValueError("--optimizer lars needs the module path (--engine module) or the CPU path; the "
                          "fused engine applies SGD inside the kernels that finish each gradient, before "
@@ -286,12 +297,29 @@ def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
                   "--batch_size, --grad_accum, --max_steps and the world size must match the run that "
                   "wrote the checkpoint", flush=True)
 
+    # the EMA starts from the parameters every rank now holds alike (loaded, or rank 0's through
+    # DDP's broadcast) and is a deterministic function of them: it needs no communication
+    ema = None
+    if opts.ema_decay:
+        from ..ops.ema import WeightEMA
+
+        ema = WeightEMA(model, decay=opts.ema_decay, warmup=opts.ema_warmup)
+        if path is not None and not resume_ema(ema, opts.checkpoint_dir, rank, world_size, device=device) \
+                and rank == 0:
+            print(f"Rank {rank}: WARNING: the checkpoint holds no weight EMA: the average restarts from the "
+                  "loaded parameters", flush=True)
+        opt.attach_ema(ema)
+
     if opts.eval_only:
         if path is None:
             raise FileNotFoundError(f"--eval_only: no checkpoint under {opts.checkpoint_dir!r}")
         # a bare model's parameters: the fused kernel's operands are built from them
         res = run_eval(model, None, edata, device, opts, rank, world_size, fused)
         _log_eval(rank, start_epoch - 1, res)
+        if opts.eval_ema:
+            with ema.applied():
+                res = run_eval(model, None, edata, device, opts, rank, world_size, fused)
+            _log_eval(rank, start_epoch - 1, res, tag="Eval EMA")
         cleanup()
         return model
 
@@ -346,12 +374,18 @@ def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
         if on_gpu:
             torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        ev = None
+        ev = ev_ema = None
         if opts.eval_every and (epoch + 1) % opts.eval_every == 0:
             ev = run_eval(model, engine, edata, device, opts, rank, world_size, fused)
             _log_eval(rank, epoch, ev)
+            if opts.eval_ema:
+                with ema.applied():
+                    ev_ema = run_eval(model, engine, edata, device, opts, rank, world_size, fused)
+                _log_eval(rank, epoch, ev_ema, tag="Eval EMA")
         _record_metrics(opts, rank, world_size, epoch, nsteps, batch_size, dt,
-                        samples_processed(nsteps, batch_size, len(sampler)), ev,
+                        samples_processed(nsteps, batch_size, len(sampler)), ev, ev_ema=ev_ema,
+                        ema_updates=ema.num_updates() if opts.metrics_json and rank == 0 and ema is not None
+                        else None,
                         clip=opt.grad_clip_stats() if opts.metrics_json and rank == 0 else None,
                         lr=opt.current_lr() if opts.metrics_json and rank == 0 and opt.lr_schedule is not None
                         else None,
@@ -416,10 +450,10 @@ def _rank0_buffers(model, world_size: int):
                 t.copy_(s)
 
 
-def _log_eval(rank: int, epoch: int, res):
+def _log_eval(rank: int, epoch: int, res, tag: str = "Eval"):
     if rank == 0:
         top5 = "" if res.correct5 is None else f" | Top-5: {100.0 * res.top5:.2f}% ({res.correct5}/{res.count})"
-        print(f"Epoch {epoch} | Eval | Loss: {res.mean_loss:.4f} | Accuracy: {100.0 * res.accuracy:.2f}% "
+        print(f"Epoch {epoch} | {tag} | Loss: {res.mean_loss:.4f} | Accuracy: {100.0 * res.accuracy:.2f}% "
               f"({res.correct}/{res.count}){top5}", flush=True)
 
 
@@ -435,14 +469,26 @@ def module_comm(comm: str) -> str:
 
 
 def replica_digest(fs, opt) -> str:
-    """SHA-1 of this rank's flat parameters and every optimizer state buffer (SGD: momentum;
-    AdamW: both moments): bitwise replica identity."""
+    """SHA-1 of this rank's flat parameters, every optimizer state buffer (SGD: momentum;
+    AdamW: both moments) and, with an attached weight EMA, its buffer and update count: bitwise
+    replica identity."""
     import hashlib
 
     h = hashlib.sha1(fs.params.detach().cpu().numpy().tobytes())
     for buf in opt.state_buffers().values():
         if buf is not None:
             h.update(buf.detach().cpu().numpy().tobytes())
+    if getattr(opt, "ema", None) is not None:
+        h.update(ema_digest(opt.ema).encode())
+    return h.hexdigest()
+
+
+def ema_digest(ema) -> str:
+    """SHA-1 of a WeightEMA's flat buffer and update count."""
+    import hashlib
+
+    h = hashlib.sha1(ema.params.detach().cpu().numpy().tobytes())
+    h.update(str(ema.num_updates()).encode())
     return h.hexdigest()
 
 
@@ -467,7 +513,8 @@ def verify_replicas(fs, opt, rank: int, world_size: int, epoch: int):
         raise RuntimeError(f"epoch {epoch}: replicas diverged across ranks ({allg}); differing tensors "
                            f"{bad}, max |diff| {worst:.3e}")
     if rank == 0:
-        print(f"Rank 0: replicas bitwise identical after epoch {epoch} ({d[:12]})", flush=True)
+        tail = "" if getattr(opt, "ema", None) is None else f", weight EMA {ema_digest(opt.ema)[:12]}"
+        print(f"Rank 0: replicas bitwise identical after epoch {epoch} ({d[:12]}{tail})", flush=True)
 
 
 def _fault_step(fault, epoch, rank):
@@ -632,12 +679,15 @@ def samples_processed(nsteps: int, batch: int, samples_per_rank: int) -> int:
     return min(nsteps * batch, samples_per_rank)
 
 
-def _record_metrics(opts, rank, ws, epoch, nsteps, batch, dt, samples, ev=None, clip=None, lr=None, trust=None):
+def _record_metrics(opts, rank, ws, epoch, nsteps, batch, dt, samples, ev=None, clip=None, lr=None, trust=None,
+                    ev_ema=None, ema_updates=None):
     """``samples``: images this rank processed in the epoch (:func:`samples_processed`);
     ``ev``: the epoch's evaluation totals, when it ran (eval_loss / eval_accuracy keys);
     ``clip``: FusedSGD.grad_clip_stats() with --clip_grad_norm (grad_norm: the last step's
     norm; clipped_steps: steps clipped so far in this run); ``trust``: FusedLARS.trust_stats()
-    (trust_ratio_min / trust_ratio_max over the adapted tensors, the epoch's last step)."""
+    (trust_ratio_min / trust_ratio_max over the adapted tensors, the epoch's last step);
+    ``ev_ema``: the evaluation totals of the averaged weights with --eval_ema (eval_ema_* keys);
+    ``ema_updates``: WeightEMA.num_updates() with --ema_decay."""
     if not opts.metrics_json or rank != 0:
         return
     import json
@@ -649,6 +699,12 @@ def _record_metrics(opts, rank, ws, epoch, nsteps, batch, dt, samples, ev=None, 
         rec["eval_loss"], rec["eval_accuracy"] = ev.mean_loss, ev.accuracy
         if ev.correct5 is not None:
             rec["eval_top5"] = ev.top5
+    if ev_ema is not None:
+        rec["eval_ema_loss"], rec["eval_ema_accuracy"] = ev_ema.mean_loss, ev_ema.accuracy
+        if ev_ema.correct5 is not None:
+            rec["eval_ema_top5"] = ev_ema.top5
+    if ema_updates is not None:
+        rec["ema_updates"] = ema_updates
     if clip is not None:
         rec["grad_norm"], rec["clipped_steps"] = clip["total_norm"], clip["clipped"]
     if lr is not None:

@@ -7,6 +7,7 @@ import torch.nn.functional as F
 
 from . import reference
 from .adamw import FusedAdamW
+from .ema import WeightEMA
 from .lars import FusedLARS
 from .lr_schedule import LRSchedule
 from .sgd import FusedSGD
@@ -26,4 +27,4 @@ class CrossEntropyLoss(nn.Module):
         return F.cross_entropy(logits, labels)
 
 
-__all__ = ["CrossEntropyLoss", "FusedAdamW", "FusedLARS", "FusedSGD", "LRSchedule", "reference"]
+__all__ = ["CrossEntropyLoss", "FusedAdamW", "FusedLARS", "FusedSGD", "LRSchedule", "WeightEMA", "reference"]

@@ -153,6 +153,8 @@ class FusedAdamW(FlatOptimizer):
         else:
             self._step_torch()
         self.steps += 1
+        if self.ema is not None:
+            self.ema.update()
 
     def _step_torch(self):
         """The kernel's operation sequence (adamw.hip) as fp32 torch ops, the scalars from the

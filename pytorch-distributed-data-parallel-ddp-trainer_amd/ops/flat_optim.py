@@ -43,8 +43,21 @@ class FlatOptimizer:
         self._reg_names = [n for n, _ in model.named_parameters()]
         self.shadows: list[tuple] = []  # (off, n, bf16 dst, kind, a, b, c)
         self.steps = 0
+        self.ema = None           # a WeightEMA updated as step()'s last act (attach_ema)
 
     # ------------------------------------------------------------------ API
+    def attach_ema(self, ema):
+        """``step()`` ends with ``ema.update()`` from now on (``None``: detach) - inside a
+        GraphedStep capture, and with gradient accumulation on boundary steps only.  The EMA's
+        ``applied()`` exchange then refreshes this optimizer's shadows too."""
+        if ema is not None and ema.flat is not self.flat:
+            raise ValueError("the EMA averages another model's parameters")
+        if self.ema is not None:
+            self.ema._opt = None
+        self.ema = ema
+        if ema is not None:
+            ema._opt = self
+
     @property
     def lr(self):
         return self.param_groups[0]["lr"]

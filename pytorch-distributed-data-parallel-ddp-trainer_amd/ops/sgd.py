@@ -74,6 +74,8 @@ class FusedSGD(FlatOptimizer):
         else:
             self._step_torch(first)
         self.steps += 1
+        if self.ema is not None:
+            self.ema.update()
 
     def _step_native(self, C, first: bool):
         g = self.param_groups[0]

@@ -9,6 +9,9 @@ the reference's (same key order, ``OrderedDict`` + ``_metadata``, SGD
 random ``.data/serialization_id`` record (tests/test_checkpoint.py compares every
 zip record with the reference's own ``epoch_0.pt``).
 
+With a weight EMA attached to the optimizer (``--ema_decay``) the dict gains a fourth key,
+``"ema"`` (``WeightEMA.state_dict()``); without one it is exactly the reference's.
+
 Fixes of the reference's resume path:
 * B6/B7/B8/B9 - the 33-broadcast per-key protocol (broken as shipped) is replaced
   by: rank 0 loads with ``weights_only=True``, then ONE broadcast of the epoch,
@@ -72,7 +75,11 @@ def build_checkpoint(epoch: int, model: torch.nn.Module, optimizer) -> dict:
         for k, v in list(s.items()):
             if torch.is_tensor(v):
                 s[k] = v.detach().to("cpu").clone(memory_format=torch.contiguous_format)
-    return {"epoch": epoch, "model": cpu_sd, "optimizer": osd}
+    ckpt = {"epoch": epoch, "model": cpu_sd, "optimizer": osd}
+    ema = getattr(optimizer, "ema", None)
+    if ema is not None:  # a fourth key with an attached weight EMA only: without one, the reference's dict
+        ckpt["ema"] = ema.state_dict()
+    return ckpt
 
 
 def save_checkpoint(ckpt_dir, epoch: int, model, optimizer) -> str:
@@ -137,6 +144,33 @@ def resume(model, optimizer, ckpt_dir="./checkpoints", rank: int = 0, world_size
                     dist.broadcast(t, src=0)
         _broadcast_optimizer(optimizer, rank, bdev, flat)
     return int(flag[1]), (str(latest) if latest is not None else "(broadcast from rank 0)")
+
+
+def resume_ema(ema, ckpt_dir="./checkpoints", rank: int = 0, world_size: int = 1, device=None) -> bool:
+    """Collective, after :func:`resume` found a checkpoint: rank 0 loads its ``"ema"`` entry into
+    ``ema`` (a WeightEMA built from the resumed parameters), then ONE broadcast of the flat
+    averaged buffer and one of the update count.  ``False`` when the checkpoint has no ``"ema"``
+    entry: ``ema`` is left as constructed, on every rank."""
+    dist_on = world_size > 1 and dist.is_initialized()
+    bdev = device if device is not None else torch.device("cpu")
+    flag = torch.zeros(2, dtype=torch.int64, device=bdev)  # [found, num_updates]
+    if rank == 0:
+        latest = discover_latest(ckpt_dir, create=False)
+        saved = load_checkpoint(latest).get("ema") if latest is not None else None
+        if saved is not None:
+            ema.load_state_dict(saved)
+            flag[0] = 1
+            flag[1] = ema.num_updates()
+    if dist_on:
+        dist.broadcast(flag, src=0)
+    if int(flag[0]) == 0:
+        return False
+    if dist_on:
+        with torch.no_grad():
+            dist.broadcast(ema.params, src=0)
+        if rank != 0:
+            ema.set_num_updates(int(flag[1]))
+    return True
 
 
 def _broadcast_optimizer(optimizer, rank: int, bdev, flat):

@@ -119,6 +119,16 @@ def parse_args(argv=None):
     p.add_argument("--eval_size", type=int, default=0,
                    help="resnet18: build a synthetic held-out split of N images (at --image_size / --num_classes) "
                         "for --eval_every / --eval_only; 0 = none")
+    p.add_argument("--ema_decay", type=float, default=0.0, metavar="D",
+                   help="keep an exponential moving average of the weights, updated by one fused kernel at the "
+                        "end of every optimizer step (inside --graph_module captures too) and saved in the "
+                        "checkpoint's \"ema\" entry (module/CPU path; 0 = off)")
+    p.add_argument("--ema_warmup", action="store_true",
+                   help="ema: update k uses the decay min(D, (1 + k) / (10 + k)), read on the device, so "
+                        "--graph_module replays follow it")
+    p.add_argument("--eval_ema", action="store_true",
+                   help="every --eval_every / --eval_only evaluation also evaluates the averaged weights "
+                        "(an extra 'Eval EMA' line; BatchNorm statistics are the live ones)")
     return p.parse_args(argv)
 
 
@@ -141,7 +151,8 @@ def main(argv=None):
                         warmup_steps=a.warmup_steps, lr_min=a.lr_min, lr_step_epochs=a.lr_step_epochs,
                         lr_gamma=a.lr_gamma, optimizer=a.optimizer, beta1=a.beta1, beta2=a.beta2,
                         adam_eps=a.adam_eps, trust_coef=a.trust_coef, lars_eps=a.lars_eps,
-                        lars_exclude=a.lars_exclude,
+                        lars_exclude=a.lars_exclude, ema_decay=a.ema_decay, ema_warmup=a.ema_warmup,
+                        eval_ema=a.eval_ema,
                         stall=tuple(float(v) for v in a.stall_at.split(":")) if a.stall_at else None,
                         fault=tuple(int(v) for v in a.fault_at.split(":")) if a.fault_at else None)
     validate_options(opts)
