@@ -307,13 +307,15 @@ void fc_bwd(const float* dL, const float* X, const float* Wf, float* dX, float* 
             int B, long K, int NO, bool mask, hipStream_t s, const FcBwdExtras& ex = FcBwdExtras());
 
 // ---- cross-entropy --------------------------------------------------------------------
+// label_smoothing in [0, 1] (torch's: eps / C over all C classes); 0 launches the kernels'
+// builds without smoothing, anything else their SMOOTH builds
 void xent(const float* part, int G, const float* bias, int C, int B, const long long* labels64,
           const int* labels32, BatchIdx bi, float* logits_out, float* dlogits, float* loss_out,
-          float* dbias, float gscale, float dbias_scale, hipStream_t s);
+          float* dbias, float gscale, float dbias_scale, hipStream_t s, float label_smoothing = 0.f);
 
 // ResNet-width heads (C > 64, labels64, no bias fold): one wave per row; false if unsupported
 bool xent_wave_rows(const float* logits, int C, int B, const long long* labels, float* dlogits,
-                    float* loss_out, float gscale, hipStream_t s);
+                    float* loss_out, float gscale, hipStream_t s, float label_smoothing = 0.f);
 
 void xent_rows(const float* part, int HW, int CH, const float* bias, int NO, int B,
                const int* labels32, BatchIdx bi, float* dlogits, float* loss_rows, float gscale,

@@ -551,13 +551,19 @@ __global__ void avgpool_bwd_kernel(const float* __restrict__ dy, int N, int HW, 
 // Mean softmax cross-entropy over [B][C] fp32 logits (C <= 1024) for wide heads: one wave
 // per row (4 rows per block, B/4 blocks) instead of one block looping over the rows.
 // Per-row losses go out write-through; the last block sums them in row order.
+// SMOOTH: label smoothing as torch's, target = keep * onehot + eps_c with keep = 1 - eps and
+// eps_c = eps / C (both rounded once on the host, by value: a captured step replays them).
+// One more wave reduction per row, S = sum_c (x_c - mx) over the C valid classes (per lane in
+// class order, then wave_sum: a fixed order), and one more subtraction per element; no extra
+// memory traffic.  SMOOTH = false is the kernel as it was: its XentSmooth is empty.
 constexpr int XR_M = 16;
+template <bool SMOOTH>
 __global__ __launch_bounds__(256) void xent_wave_rows_kernel(const float* __restrict__ logits, int C,
                                                              int B, const long long* __restrict__ labels,
                                                              float* __restrict__ dlogits,
                                                              float* __restrict__ loss_out,
                                                              float* __restrict__ ws, int* __restrict__ ticket,
-                                                             float gscale) {
+                                                             float gscale, XentSmooth<SMOOTH> sm) {
   __shared__ int s_last;
   const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b < B) {
@@ -571,25 +577,38 @@ __global__ __launch_bounds__(256) void xent_wave_rows_kernel(const float* __rest
       mx = fmaxf(mx, x[m]);
     }
     mx = wave_max(mx);
-    float se = 0.f, xl = 0.f;
+    float se = 0.f, xl = 0.f, sx = 0.f;
 #pragma unroll
     for (int m = 0; m < XR_M; ++m) {
       const int c = lane + 64 * m;
       if (c == label) xl = x[m];
+      if constexpr (SMOOTH) {
+        if (c < C) sx += x[m] - mx;  // lanes / steps past C add exactly 0, not -inf
+      }
       x[m] = c < C ? __expf(x[m] - mx) : 0.f;
       se += x[m];
     }
     se = wave_sum(se);
     xl = wave_sum(xl);  // logit[label]
+    if constexpr (SMOOTH) sx = wave_sum(sx);  // S = sum_c (x_c - mx)
     const float inv = 1.f / se;
 #pragma unroll
     for (int m = 0; m < XR_M; ++m) {
       const int c = lane + 64 * m;
-      if (c < C) dlogits[(long)b * C + c] = (x[m] * inv - (c == label ? 1.f : 0.f)) * gscale;
+      if constexpr (SMOOTH) {
+        if (c < C) dlogits[(long)b * C + c] = ((x[m] * inv - (c == label ? sm.keep : 0.f)) - sm.eps_c) * gscale;
+      } else {
+        if (c < C) dlogits[(long)b * C + c] = (x[m] * inv - (c == label ? 1.f : 0.f)) * gscale;
+      }
     }
     // log(se) - (xl - mx), not (mx + log(se)) - xl: the latter rounds at the logits' own
     // magnitude (an offset of 1e4 costs 5e-4 of the row's loss), xl - mx is (nearly) exact
-    if (lane == 0) st_wt(ws + b, __logf(se) - (xl - mx));
+    if constexpr (SMOOTH) {
+      // log(se) - [keep (xl - mx) + eps_c S]: every term relative to the row maximum, as above
+      if (lane == 0) st_wt(ws + b, __logf(se) - fmaf(sm.eps_c, sx, sm.keep * (xl - mx)));
+    } else {
+      if (lane == 0) st_wt(ws + b, __logf(se) - (xl - mx));
+    }
   }
   if (!last_arrival(ticket, gridDim.x, &s_last)) return;
   if (threadIdx.x == 0) {
@@ -843,7 +862,7 @@ void avgpool_fwd(const bf16_t* x, int N, int HW, int C, float* y, hipStream_t s)
 }
 
 bool xent_wave_rows(const float* logits, int C, int B, const long long* labels, float* dlogits,
-                    float* loss_out, float gscale, hipStream_t s) {
+                    float* loss_out, float gscale, hipStream_t s, float label_smoothing) {
   constexpr int kMaxB = 8192;
   if (C > 64 * XR_M || B > kMaxB || B < 1) return false;
   static float* wsp[64] = {};
@@ -851,8 +870,14 @@ bool xent_wave_rows(const float* logits, int C, int B, const long long* labels, 
   RN_CHECK(hipGetDevice(&dev));
   dev &= 63;
   if (!wsp[dev]) RN_CHECK(hipMalloc(reinterpret_cast<void**>(&wsp[dev]), sizeof(float) * kMaxB));
-  hipLaunchKernelGGL(xent_wave_rows_kernel, dim3((B + 3) / 4), dim3(256), 0, s, logits, C, B, labels,
-                     dlogits, loss_out, wsp[dev], bn_ticket_slots(1), gscale);
+  // label_smoothing == 0 launches the build without smoothing: the kernel as it always was
+  if (label_smoothing != 0.f)
+    hipLaunchKernelGGL(xent_wave_rows_kernel<true>, dim3((B + 3) / 4), dim3(256), 0, s, logits, C, B, labels,
+                       dlogits, loss_out, wsp[dev], bn_ticket_slots(1), gscale,
+                       XentSmooth<true>{1.f - label_smoothing, label_smoothing / (float)C});
+  else
+    hipLaunchKernelGGL(xent_wave_rows_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, s, logits, C, B, labels,
+                       dlogits, loss_out, wsp[dev], bn_ticket_slots(1), gscale, XentSmooth<false>{});
   return true;
 }
 

@@ -36,6 +36,16 @@ struct BatchIdx {
   }
 };
 
+// Label smoothing of the cross-entropy kernels' SMOOTH builds, by value: keep = 1 - eps and
+// eps_c = eps / C, each rounded once on the host.  The builds without smoothing take the
+// empty struct: no argument bytes they would have to skip.
+template <bool SMOOTH>
+struct XentSmooth {};
+template <>
+struct XentSmooth<true> {
+  float keep, eps_c;
+};
+
 // Source of SimpleCNN's first-layer activation when a kernel recomputes it on the fly
 // (a1 = relu(conv1(x0[idx])) / bf16) instead of reading a stored a1 tensor.
 struct C1Src {

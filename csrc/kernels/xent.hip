@@ -18,6 +18,13 @@ namespace ddp_amd {
 
 constexpr int XE_MAXM = 16;  // up to 1024 classes
 
+// SMOOTH: label smoothing as torch's (the mass eps goes over all C classes, the true one
+// included): target = keep * onehot + eps_c, keep = 1 - eps and eps_c = eps / C rounded once
+// on the host and passed by value.  loss_b = log(se) - [keep (xl - mx) + eps_c S] with
+// S = sum_c (x_c - mx) over the valid classes (per lane in class order, then wave_sum),
+// dlogits = (softmax - keep * onehot - eps_c) * gscale; dbias sums those.  SMOOTH = false is
+// the kernel as it was (its XentSmooth is empty).
+template <bool SMOOTH>
 __global__ __launch_bounds__(1024) void xent_kernel(const float* __restrict__ part, int G,
                                                    const float* __restrict__ bias, int C, int B,
                                                    const long long* __restrict__ labels64,
@@ -26,7 +33,7 @@ __global__ __launch_bounds__(1024) void xent_kernel(const float* __restrict__ pa
                                                    float* __restrict__ dlogits,
                                                    float* __restrict__ loss_out,
                                                    float* __restrict__ dbias, float gscale,
-                                                   float dbias_scale) {
+                                                   float dbias_scale, XentSmooth<SMOOTH> sm) {
   __shared__ float s_loss[16];
   __shared__ float s_db[4][XE_MAXM * 64];  // dbias: 4 waves only (see xent())
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
@@ -53,28 +60,43 @@ __global__ __launch_bounds__(1024) void xent_kernel(const float* __restrict__ pa
       }
     }
     mx = wave_max(mx);
-    float se = 0.f, xl = 0.f;
+    float se = 0.f, xl = 0.f, sx = 0.f;
 #pragma unroll
     for (int m = 0; m < XE_MAXM; ++m) {
       const int c = lane + 64 * m;
       if (m < M && c < C) {
         se += __expf(x[m] - mx);
         if (c == label) xl = x[m];
+        if constexpr (SMOOTH) sx += x[m] - mx;  // valid classes only: the rest add exactly 0
       }
     }
     se = wave_sum(se);
     xl = wave_sum(xl);
     // log(se) - (xl - mx), not (mx + log(se)) - xl: the latter rounds at the logits' own
     // magnitude (an offset of 1e4 costs 5e-4 of the row's loss), xl - mx is (nearly) exact
-    lsum += __logf(se) - (xl - mx);
+    if constexpr (SMOOTH) {
+      sx = wave_sum(sx);  // S = sum_c (x_c - mx)
+      lsum += __logf(se) - fmaf(sm.eps_c, sx, sm.keep * (xl - mx));
+    } else {
+      lsum += __logf(se) - (xl - mx);
+    }
     const float inv = 1.f / se;
 #pragma unroll
     for (int m = 0; m < XE_MAXM; ++m) {
       const int c = lane + 64 * m;
       if (m < M && c < C) {
-        const float d = (__expf(x[m] - mx) * inv - (c == label ? 1.f : 0.f)) * gscale;
+        float d;
+        if constexpr (SMOOTH)
+          d = ((__expf(x[m] - mx) * inv - (c == label ? sm.keep : 0.f)) - sm.eps_c) * gscale;
+        else
+          d = (__expf(x[m] - mx) * inv - (c == label ? 1.f : 0.f)) * gscale;
         dlogits[(long)b * C + c] = d;
-        db[m] += d;
+        if constexpr (SMOOTH) {
+#pragma clang fp contract(off)  // dbias: the in-order sum of the stored dlogits, bit for bit
+          db[m] += d;
+        } else {
+          db[m] += d;
+        }
       }
     }
   }
@@ -121,14 +143,20 @@ void xent_rows(const float* part, int HW, int CH, const float* bias, int NO, int
 
 void xent(const float* part, int G, const float* bias, int C, int B, const long long* labels64,
           const int* labels32, BatchIdx bi, float* logits_out, float* dlogits, float* loss_out,
-          float* dbias, float gscale, float dbias_scale, hipStream_t s) {
+          float* dbias, float gscale, float dbias_scale, hipStream_t s, float label_smoothing) {
   // one wave per row when there is no bias gradient to fold (it is reduced over 4 waves)
   if (G == 1 && !bias && !dbias && !logits_out && labels64 && !bi.step_ctr && C > 64 &&
-      xent_wave_rows(part, C, B, labels64, dlogits, loss_out, gscale, s))
+      xent_wave_rows(part, C, B, labels64, dlogits, loss_out, gscale, s, label_smoothing))
     return;
   const int waves = dbias ? 4 : (B < 16 ? (B < 4 ? 4 : B) : 16);
-  hipLaunchKernelGGL(xent_kernel, dim3(1), dim3(64 * waves), 0, s, part, G, bias, C, B, labels64, labels32,
-                     bi, logits_out, dlogits, loss_out, dbias, gscale, dbias_scale);
+  // label_smoothing == 0 launches the build without smoothing: the kernel as it always was
+  if (label_smoothing != 0.f)
+    hipLaunchKernelGGL(xent_kernel<true>, dim3(1), dim3(64 * waves), 0, s, part, G, bias, C, B, labels64,
+                       labels32, bi, logits_out, dlogits, loss_out, dbias, gscale, dbias_scale,
+                       XentSmooth<true>{1.f - label_smoothing, label_smoothing / (float)C});
+  else
+    hipLaunchKernelGGL(xent_kernel<false>, dim3(1), dim3(64 * waves), 0, s, part, G, bias, C, B, labels64,
+                       labels32, bi, logits_out, dlogits, loss_out, dbias, gscale, dbias_scale, XentSmooth<false>{});
 }
 
 DDP_STAMPS_SETTER(stamps_set_xent)

@@ -95,6 +95,7 @@ class TrainOptions:
     ema_decay: float = 0.0            # weight EMA updated by every optimizer step (0: off; module/CPU path)
     ema_warmup: bool = False          # decay_k = min(ema_decay, (1 + k) / (10 + k)) for update k
     eval_ema: bool = False            # every evaluation also evaluates the averaged weights
+    label_smoothing: float = 0.0      # training loss target (1 - e) onehot + e / C, torch's (0: off; module/CPU path)
 
 
 def validate_options(opts: TrainOptions):
@@ -129,6 +130,8 @@ def validate_options(opts: TrainOptions):
         raise ValueError("--ema_decay must lie in [0, 1) (0 = off)")
     if (opts.eval_ema or opts.ema_warmup) and not opts.ema_decay:
         raise ValueError("--eval_ema / --ema_warmup need a weight EMA: set --ema_decay D")
+    if not 0.0 <= opts.label_smoothing <= 1.0:
+        raise ValueError("--label_smoothing must lie in [0, 1] (0 = off)")
     if opts.optimizer == "adamw" and opts.momentum != 0:
         raise ValueError("--momentum is SGD's; --optimizer adamw takes --beta1 / --beta2 / --adam_eps")
     if (opts.device or "").lower() == "gpu":  # the fused engine is certain: refuse before any process starts
@@ -152,6 +155,10 @@ def check_fused_engine_options(opts: TrainOptions, fused: bool):
         raise ValueError("--ema_decay needs the module path (--engine module) or the CPU path; the fused "
                          "engine applies SGD inside the kernels that finish each gradient and its captured "
                          "step graphs hold no averaging pass")
+    if fused and opts.label_smoothing:
+        raise ValueError("--label_smoothing needs the module path (--engine module) or the CPU path; the "
+                         "fused engine computes its loss inside the forward and fc_bwd kernels, which have "
+                         "no smoothed build")
     if fused and opts.optimizer == "lars":
         raise ValueError("--optimizer lars needs the module path (--engine module) or the CPU path; the "
                          "fused engine applies SGD inside the kernels that finish each gradient, before "
@@ -253,7 +260,9 @@ def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
         if rank == 0:
             print(f"Rank {rank}: Eval split: {tsrc} ({len(edata)} images)", flush=True)
     print(f"Rank {rank}: Dataloader ready", flush=True)
-    loss_fn = CrossEntropyLoss()
+    # the training loss only: evaluation keeps reporting the plain cross-entropy, so evaluation
+    # losses stay comparable between runs with different --label_smoothing
+    loss_fn = CrossEntropyLoss(label_smoothing=opts.label_smoothing)
     # clipping lives in opt.step(): with --grad_accum only the boundary step clips, and under
     # DDP the norm is of the all-reduced gradient (the same bits, so the same coefficient, on every rank)
     # the schedule is indexed by the global optimizer step: a table every rank builds alike from the
@@ -703,6 +712,8 @@ def _record_metrics(opts, rank, ws, epoch, nsteps, batch, dt, samples, ev=None, 
         rec["eval_ema_loss"], rec["eval_ema_accuracy"] = ev_ema.mean_loss, ev_ema.accuracy
         if ev_ema.correct5 is not None:
             rec["eval_ema_top5"] = ev_ema.top5
+    if opts.label_smoothing:
+        rec["label_smoothing"] = opts.label_smoothing
     if ema_updates is not None:
         rec["ema_updates"] = ema_updates
     if clip is not None:

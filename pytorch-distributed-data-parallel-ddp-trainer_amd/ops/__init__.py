@@ -14,17 +14,28 @@ from .sgd import FusedSGD
 
 
 class CrossEntropyLoss(nn.Module):
-    """``nn.CrossEntropyLoss()`` (mean) - fused HIP softmax-xent on the GPU.
+    """``nn.CrossEntropyLoss(label_smoothing=eps)`` (mean) - fused HIP softmax-xent on the GPU.
 
-    Reference: train_ddp.py:40 ``loss_fn = nn.CrossEntropyLoss()``.
+    Reference: train_ddp.py:40 ``loss_fn = nn.CrossEntropyLoss()``.  ``label_smoothing`` is
+    torch's: the target is ``(1 - eps) * onehot + eps / C`` over all C classes, computed inside
+    the kernels' SMOOTH builds (0, the default, runs the kernels without it).
     """
+
+    def __init__(self, label_smoothing: float = 0.0):
+        super().__init__()
+        if not 0.0 <= label_smoothing <= 1.0:  # NaN fails too
+            raise ValueError(f"label_smoothing must lie in [0, 1], got {label_smoothing!r}")
+        self.label_smoothing = float(label_smoothing)
 
     def forward(self, logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
         if logits.is_cuda:
             from .functional import cross_entropy
 
-            return cross_entropy(logits, labels)
-        return F.cross_entropy(logits, labels)
+            return cross_entropy(logits, labels, self.label_smoothing)
+        return F.cross_entropy(logits, labels, label_smoothing=self.label_smoothing)
+
+    def extra_repr(self) -> str:
+        return f"label_smoothing={self.label_smoothing}" if self.label_smoothing else ""
 
 
 __all__ = ["CrossEntropyLoss", "FusedAdamW", "FusedLARS", "FusedSGD", "LRSchedule", "WeightEMA", "reference"]

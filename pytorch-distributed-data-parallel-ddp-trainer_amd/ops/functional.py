@@ -8,7 +8,8 @@ op                   forward kernel                              backward kernel
 conv1_relu           conv1_fwd (VALU, Cin=1, bias+ReLU fused)    conv1_wgrad (+ReLU mask) -> grad_reduce
 conv3x3_relu         conv3x3_fwd (MFMA, bias+ReLU fused)         conv3x3_dgrad (+mask), conv3x3_wgrad -> grad_reduce
 linear_nhwc          fc_partial + fc_reduce (split-K, fixed)     fc_bwd (dgrad+wgrad in one pass)
-cross_entropy        xent (softmax-xent fwd+bwd fused)           scale of the saved dlogits
+cross_entropy        xent (softmax-xent fwd+bwd fused,           scale of the saved dlogits
+                     label smoothing by value)
 ===================  ==========================================  ==============================
 
 Activations are NHWC in the compute dtype: bf16 (default; fp32 masters converted to bf16
@@ -147,19 +148,23 @@ class _LinearNHWC(torch.autograd.Function):
 
 class _CrossEntropy(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, labels):
+    def forward(ctx, logits, labels, label_smoothing=0.0):
         B, C = logits.shape
         lg = logits.float().contiguous()
         dl = torch.empty_like(lg)
         loss = torch.empty(1, dtype=torch.float32, device=lg.device)
-        _C().xent(lg, 1, None, labels.contiguous(), None, dl, loss, None, 1.0 / B, 0.0)
+        # a run constant passed by value: a captured step replays it without device state
+        # (0: the ten-argument call as it always was, which an older build of the extension,
+        # loaded as an A/B variant, also takes)
+        kw = {"label_smoothing": float(label_smoothing)} if label_smoothing else {}
+        _C().xent(lg, 1, None, labels.contiguous(), None, dl, loss, None, 1.0 / B, 0.0, **kw)
         ctx.save_for_backward(dl)
         return loss.reshape(())
 
     @staticmethod
     def backward(ctx, g):
         (dl,) = ctx.saved_tensors
-        return dl * g, None
+        return dl * g, None, None
 
 
 def conv1_relu(x, w, b, dtype=BF16):
@@ -174,8 +179,9 @@ def linear_nhwc(x, w, b, dtype=BF16):
     return _LinearNHWC.apply(x, w, b, dtype)
 
 
-def cross_entropy(logits, labels):
-    return _CrossEntropy.apply(logits, labels)
+def cross_entropy(logits, labels, label_smoothing=0.0):
+    """Mean softmax cross-entropy; ``label_smoothing`` as torch's (eps / C over all C classes)."""
+    return _CrossEntropy.apply(logits, labels, label_smoothing)
 
 
 def fc_weight_frag(w: torch.Tensor, hw: int, c: int, dtype=torch.bfloat16) -> torch.Tensor:

@@ -81,16 +81,24 @@ def fc_bwd(dl, x_nhwc, w_native, mask=True):
     return dx.view_as(x_nhwc), dw.view_as(w_native)
 
 
-def cross_entropy(logits, labels):
-    """(mean loss, dlogits = (softmax - onehot)/B)."""
+def cross_entropy(logits, labels, label_smoothing=0.0):
+    """(mean loss, dlogits = (softmax - onehot)/B); with ``label_smoothing`` = eps the target is
+    (1 - eps) onehot + eps / C over all C classes (torch's)."""
     lp = torch.log_softmax(_f(logits), dim=1)
     loss = F.nll_loss(lp, labels)
     d = lp.exp()
-    d[torch.arange(logits.shape[0]), labels] -= 1.0
+    if label_smoothing:
+        eps, C = float(label_smoothing), logits.shape[1]
+        loss = (1.0 - eps) * loss + (eps / C) * (-lp.sum(1)).mean()
+        d[torch.arange(logits.shape[0]), labels] -= 1.0 - eps
+        d -= eps / C
+    else:
+        d[torch.arange(logits.shape[0]), labels] -= 1.0
     return loss, d / logits.shape[0]
 
 
-def simple_cnn_step_bf16(params: dict, x: torch.Tensor, labels: torch.Tensor, ws: int = 1):
+def simple_cnn_step_bf16(params: dict, x: torch.Tensor, labels: torch.Tensor, ws: int = 1,
+                         label_smoothing: float = 0.0):
     """fp32 PyTorch model of ONE SimpleCNN training step that rounds to bf16 at exactly
     the points the HIP pipeline stores bf16 (activations, MFMA operands, dZ tensors).
 
@@ -105,7 +113,7 @@ def simple_cnn_step_bf16(params: dict, x: torch.Tensor, labels: torch.Tensor, ws
     a1 = bf16r(conv1_relu(x.float(), w1, b1))                      # [B,28,28,32]
     a2 = bf16r(conv3x3(a1, w2b, b2, relu=True))                     # [B,28,28,64]
     logits = fc_nhwc(a2, wfcb, bfc)
-    loss, dl = cross_entropy(logits, labels)
+    loss, dl = cross_entropy(logits, labels, label_smoothing)
     dz2 = bf16r((dl @ wfcb.reshape(wfcb.shape[0], -1)).view_as(a2) * (a2 > 0))
     dwfc = (dl.t() @ a2.reshape(B, -1)).view_as(wfc)
     dw2, db2 = conv3x3_wgrad(dz2, a1)
@@ -117,7 +125,7 @@ def simple_cnn_step_bf16(params: dict, x: torch.Tensor, labels: torch.Tensor, ws
 
 
 def simple_cnn_step_exact(params: dict, x: torch.Tensor, labels: torch.Tensor, ws: int = 1,
-                          dtype: torch.dtype = torch.float64):
+                          dtype: torch.dtype = torch.float64, label_smoothing: float = 0.0):
     """The same step without any bf16 rounding, evaluated in ``dtype`` (float64 by
     default): the oracle of the exact-fp32 path (``--dtype fp32``), whose MFMA results
     are plain fp32 fma chains.  Same arguments / returns as :func:`simple_cnn_step_bf16`."""
@@ -128,7 +136,7 @@ def simple_cnn_step_exact(params: dict, x: torch.Tensor, labels: torch.Tensor, w
     a1 = conv1_relu(x, w1, b1)
     a2 = conv3x3(a1, w2, b2, relu=True)
     logits = fc_nhwc(a2, wfc, bfc)
-    loss, dl = cross_entropy(logits, labels)
+    loss, dl = cross_entropy(logits, labels, label_smoothing)
     dz2 = (dl @ wfc.reshape(wfc.shape[0], -1)).view_as(a2) * (a2 > 0)
     dwfc = (dl.t() @ a2.reshape(B, -1)).view_as(wfc)
     dw2, db2 = conv3x3_wgrad(dz2, a1)
@@ -229,21 +237,33 @@ def avgpool_bwd64(dy, H, W):
     return (dy / (H * W))[:, None, None, :].expand(dy.shape[0], H, W, dy.shape[1]).contiguous()
 
 
-def xent_rows64(logits, labels):
-    """Per-row softmax cross-entropy: (loss [B], softmax p [B,C])."""
+def xent_rows64(logits, labels, label_smoothing=0.0):
+    """Per-row softmax cross-entropy: (loss [B], softmax p [B,C]).  ``label_smoothing`` = eps:
+    the target is (1 - eps) onehot + eps / C over all C classes (torch's), so the row loss is
+    logsumexp(x) - (1 - eps) x_y - (eps / C) sum_c x_c, written here from that definition."""
     x = _d(logits)
     lab = labels.detach().cpu().long()
     z = x - x.max(1, keepdim=True).values
     lse = z.exp().sum(1).log()
-    return lse - z[torch.arange(x.shape[0]), lab], (z - lse[:, None]).exp()
+    zl = z[torch.arange(x.shape[0]), lab]
+    if not label_smoothing:
+        return lse - zl, (z - lse[:, None]).exp()
+    eps = float(label_smoothing)
+    return lse - ((1.0 - eps) * zl + (eps / x.shape[1]) * z.sum(1)), (z - lse[:, None]).exp()
 
 
-def xent64(logits, labels, gscale=None):
-    """(mean loss, dlogits = (softmax - onehot) * gscale); gscale defaults to 1 / B."""
-    loss, p = xent_rows64(logits, labels)
-    B = p.shape[0]
+def xent64(logits, labels, gscale=None, label_smoothing=0.0):
+    """(mean loss, dlogits = (softmax - (1 - eps) onehot - eps / C) * gscale); gscale defaults
+    to 1 / B, eps = ``label_smoothing`` to 0."""
+    loss, p = xent_rows64(logits, labels, label_smoothing)
+    B, C = p.shape
     d = p.clone()
-    d[torch.arange(B), labels.detach().cpu().long()] -= 1.0
+    if label_smoothing:
+        eps = float(label_smoothing)
+        d[torch.arange(B), labels.detach().cpu().long()] -= 1.0 - eps
+        d -= eps / C
+    else:
+        d[torch.arange(B), labels.detach().cpu().long()] -= 1.0
     return loss.mean(), d * (1.0 / B if gscale is None else gscale)
 
 

@@ -81,6 +81,10 @@ def parse_args(argv=None):
     p.add_argument("--clip_grad_norm", type=float, default=0.0, metavar="X",
                    help="clip the global gradient L2 norm to X inside the optimizer step, as "
                         "torch.nn.utils.clip_grad_norm_ (module/CPU path; 0 = off)")
+    p.add_argument("--label_smoothing", type=float, default=0.0, metavar="E",
+                   help="train against the target (1 - E) * onehot + E / C over all C classes, as "
+                        "torch.nn.CrossEntropyLoss(label_smoothing=E), inside the fused cross-entropy kernels "
+                        "(module/CPU path; 0 = off; evaluation losses stay the plain cross-entropy)")
     p.add_argument("--lr_schedule", choices=["none", "cosine", "linear", "step"], default="none",
                    help="learning-rate decay per optimizer step over --epochs (after --warmup_steps): cosine or "
                         "linear down to --lr_min, or times --lr_gamma every --lr_step_epochs epochs; read on the "
@@ -152,7 +156,7 @@ def main(argv=None):
                         lr_gamma=a.lr_gamma, optimizer=a.optimizer, beta1=a.beta1, beta2=a.beta2,
                         adam_eps=a.adam_eps, trust_coef=a.trust_coef, lars_eps=a.lars_eps,
                         lars_exclude=a.lars_exclude, ema_decay=a.ema_decay, ema_warmup=a.ema_warmup,
-                        eval_ema=a.eval_ema,
+                        eval_ema=a.eval_ema, label_smoothing=a.label_smoothing,
                         stall=tuple(float(v) for v in a.stall_at.split(":")) if a.stall_at else None,
                         fault=tuple(int(v) for v in a.fault_at.split(":")) if a.fault_at else None)
     validate_options(opts)
