@@ -222,6 +222,15 @@ void maxpool_bwd(const bf16_t* dy, const unsigned char* amax, int N, int H, int 
                  int OW, bf16_t* dx, hipStream_t s, const bf16_t* dy2 = nullptr);
 void image_gather_nhwc4(const unsigned char* imgs, const long long* idx, int B, int HW, long N,
                         bf16_t* out, hipStream_t s);
+// the augmenting / normalising gather: params [N][5] int32 = (top, left, h, w, flip) per data-set
+// image; a pixel of uint8 value v in channel c becomes bf16(fmaf(v, a[c], b[c])); resample: the
+// bilinear (random-resized-crop) build, else the shift / zero-fill / flip build
+struct GatherAffine {
+  float a[3], b[3];
+};
+void image_gather_aug_nhwc4(const unsigned char* imgs, const long long* idx, const int* params, int B,
+                            int H, int W, long N, const GatherAffine& aff, bool resample, bf16_t* out,
+                            hipStream_t s);
 void avgpool_fwd(const bf16_t* x, int N, int HW, int C, float* y, hipStream_t s);
 void avgpool_bwd(const float* dy, int N, int HW, int C, bf16_t* dx, hipStream_t s);
 // accum: C += alpha A.B (+ bias) instead of C =

@@ -637,6 +637,135 @@ __global__ __launch_bounds__(256) void image_gather_nhwc4_kernel(const unsigned 
   *reinterpret_cast<uint2*>(out + i * 4) = pack4(src[0] * k, src[1] * k, src[2] * k, 0.f);
 }
 
+// The same gather with the train augmentation and the normalisation folded in: output pixel
+// (r, c) of batch row b reads image n = idx[b] through the image's row of the parameter table
+// params[N][GA_COLS] = (top, left, h, w, flip) and becomes fmaf(v, a_c, b_c) -> bf16.
+//   RESAMPLE = false: v = source pixel (r + top, c' + left), c' = flip ? W - 1 - c : c; top and
+//     left may be negative (random crop with padding) and a source pixel outside the image is
+//     a black uint8 pixel, v = 0, BEFORE the fma (h, w are H, W and unused).
+//   RESAMPLE = true: the box (top, left, h, w) inside the image is resampled to H x W,
+//     bilinear, align_corners = False, no antialias, in the fp32 operation order the README's
+//     Augmentation section states (every step an explicit fmaf: nothing for the compiler to contract).
+// A thread owns GA_PX = 4 adjacent output pixels of one row: 32 stored bytes (two 16-byte
+// stores when the row's base allows it).  In the integer build its 12 source bytes are
+// contiguous with or without a flip (a flipped run reads the mirrored run, reversed), so they
+// come in as the 4 aligned dwords around them, shifted into place with v_alignbyte - 4 loads
+// per 32 stored bytes where the plain kernel issues 12.  The dword window may hang over the
+// run's ends into the neighbouring pixels of the same allocation; it is loaded only when all
+// 16 bytes lie inside [imgs, imgs + N*H*W*3), the columns outside the image are zeroed by
+// predicate afterwards, and a run at the very edge of the allocation (or in a padded row)
+// takes predicated byte loads / no loads instead: no address outside the tensor is ever read.
+// blockIdx.x = b * blocks_per_image + block: b, n and the table row are block-uniform.
+constexpr int GA_PX = 4;
+constexpr int GA_COLS = 5;
+
+template <bool RESAMPLE>
+__global__ __launch_bounds__(256) void image_gather_aug_nhwc4_kernel(const unsigned char* __restrict__ imgs,
+                                                                     const long long* __restrict__ idx,
+                                                                     const int* __restrict__ params,
+                                                                     int H, int W, long N, int runs_per_row,
+                                                                     int blocks_per_image, GatherAffine aff,
+                                                                     bf16_t* __restrict__ out) {
+  const int b = blockIdx.x / blocks_per_image;
+  const int run = (blockIdx.x - b * blocks_per_image) * 256 + threadIdx.x;
+  if (run >= H * runs_per_row) return;
+  const int r = run / runs_per_row;
+  const int c0 = (run - r * runs_per_row) * GA_PX;
+  const int npx = min(GA_PX, W - c0);
+  long n = idx[b];
+  n = n < 0 ? 0 : (n >= N ? N - 1 : n);  // host validates; never read out of bounds
+  const int* pr = params + n * GA_COLS;
+  const int top = pr[0], left = pr[1];
+  const bool flip = pr[4] != 0;
+  const long img = n * H * W * 3;  // byte offset of image n
+  uint2 o[GA_PX];
+
+  if constexpr (!RESAMPLE) {
+    const int sr = r + top;
+    // source columns s0 .. s0 + 3 in memory order; flipped, output pixel k shows s0 + 3 - k
+    const int s0 = (flip ? W - GA_PX - c0 : c0) + left;
+    const bool row_ok = (unsigned)sr < (unsigned)H;
+    unsigned e[3] = {0u, 0u, 0u};  // the run's 12 source bytes
+    if (row_ok) {
+      const long off = img + ((long)sr * W + s0) * 3;  // (negative only in image 0: s0 < 0)
+      const unsigned sh = (unsigned)(((unsigned long long)imgs + (unsigned long long)off) & 3ull);
+      const long q = off - (long)sh;  // the dword-aligned window's first byte
+      if (q >= 0 && q + 16 <= N * H * W * 3) {
+        const unsigned* qd = reinterpret_cast<const unsigned*>(imgs + q);
+        const unsigned d0 = qd[0], d1 = qd[1], d2 = qd[2], d3 = qd[3];
+        e[0] = __builtin_amdgcn_alignbyte(d1, d0, sh);
+        e[1] = __builtin_amdgcn_alignbyte(d2, d1, sh);
+        e[2] = __builtin_amdgcn_alignbyte(d3, d2, sh);
+      } else {  // the first / last bytes of the data set
+#pragma unroll
+        for (int j = 0; j < GA_PX; ++j) {
+          if ((unsigned)(s0 + j) >= (unsigned)W) continue;
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const int t = 3 * j + c;
+            e[t >> 2] |= (unsigned)imgs[off + t] << (8 * (t & 3));
+          }
+        }
+      }
+    }
+    float v[GA_PX][3];
+#pragma unroll
+    for (int j = 0; j < GA_PX; ++j) {
+      const bool ok = row_ok && (unsigned)(s0 + j) < (unsigned)W;  // else: the padding's black pixel
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int t = 3 * j + c;
+        v[j][c] = ok ? (float)((e[t >> 2] >> (8 * (t & 3))) & 0xffu) : 0.f;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < GA_PX; ++k) {
+      float w[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) w[c] = fmaf(flip ? v[GA_PX - 1 - k][c] : v[k][c], aff.a[c], aff.b[c]);
+      o[k] = pack4(w[0], w[1], w[2], 0.f);
+    }
+  } else {
+    const int bh = pr[2], bw = pr[3];
+    // predicated tap: a table row that does not describe a box inside the image reads zeros
+    auto tap = [&](int y, int x, int c) -> float {
+      const int gy = top + y, gx = left + x;
+      return ((unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W)
+                 ? (float)imgs[img + ((long)gy * W + gx) * 3 + c] : 0.f;
+    };
+    const float sy = (float)bh / (float)H, sx = (float)bw / (float)W;  // IEEE divisions
+    const float ys = fmaxf(fmaf((float)r + 0.5f, sy, -0.5f), 0.f);
+    const int y0 = min((int)ys, bh - 1), y1 = min(y0 + 1, bh - 1);
+    const float ly = ys - (float)y0;
+#pragma unroll
+    for (int k = 0; k < GA_PX; ++k) {
+      if (k >= npx) break;
+      const int cc = flip ? W - 1 - (c0 + k) : c0 + k;
+      const float xs = fmaxf(fmaf((float)cc + 0.5f, sx, -0.5f), 0.f);
+      const int x0 = min((int)xs, bw - 1), x1 = min(x0 + 1, bw - 1);
+      const float lx = xs - (float)x0;
+      float w[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float v00 = tap(y0, x0, c), v01 = tap(y0, x1, c), v10 = tap(y1, x0, c), v11 = tap(y1, x1, c);
+        const float t = fmaf(lx, v01 - v00, v00), bt = fmaf(lx, v11 - v10, v10);
+        w[c] = fmaf(fmaf(ly, bt - t, t), aff.a[c], aff.b[c]);
+      }
+      o[k] = pack4(w[0], w[1], w[2], 0.f);
+    }
+  }
+
+  bf16_t* dst = out + (((long)b * H + r) * W + c0) * 4;
+  if (npx == GA_PX && ((unsigned long long)dst & 15ull) == 0) {
+    reinterpret_cast<uint4*>(dst)[0] = make_uint4(o[0].x, o[0].y, o[1].x, o[1].y);
+    reinterpret_cast<uint4*>(dst)[1] = make_uint4(o[2].x, o[2].y, o[3].x, o[3].y);
+  } else {  // a row tail, or rows of an odd W that start 8 bytes off
+#pragma unroll
+    for (int k = 0; k < GA_PX; ++k)
+      if (k < npx) reinterpret_cast<uint2*>(dst)[k] = o[k];
+  }
+}
+
 // ---------------------------------------------------------------- small fp32 GEMM
 // C[m][n] = alpha * sum_k A(m,k) B(k,n) + (bias ? bias[n] : 0), A(m,k) = A[m*sam + k*sak],
 // B(k,n) = B[k*sbk + n*sbn]; A/B element type float or bf16 (template).  16x16 LDS
@@ -855,6 +984,20 @@ void image_gather_nhwc4(const unsigned char* imgs, const long long* idx, int B, 
   const long total = (long)B * HW;
   hipLaunchKernelGGL(image_gather_nhwc4_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
                      imgs, idx, B, HW, N, out);
+}
+
+void image_gather_aug_nhwc4(const unsigned char* imgs, const long long* idx, const int* params, int B,
+                            int H, int W, long N, const GatherAffine& aff, bool resample, bf16_t* out,
+                            hipStream_t s) {
+  const int runs_per_row = (W + GA_PX - 1) / GA_PX;
+  const int blocks_per_image = (H * runs_per_row + 255) / 256;
+  const dim3 grid((unsigned)((long)B * blocks_per_image));
+  if (resample)
+    hipLaunchKernelGGL(image_gather_aug_nhwc4_kernel<true>, grid, dim3(256), 0, s, imgs, idx, params, H, W, N,
+                       runs_per_row, blocks_per_image, aff, out);
+  else
+    hipLaunchKernelGGL(image_gather_aug_nhwc4_kernel<false>, grid, dim3(256), 0, s, imgs, idx, params, H, W, N,
+                       runs_per_row, blocks_per_image, aff, out);
 }
 
 void avgpool_fwd(const bf16_t* x, int N, int HW, int C, float* y, hipStream_t s) {

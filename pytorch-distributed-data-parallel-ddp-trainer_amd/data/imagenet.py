@@ -9,12 +9,16 @@ Like the MNIST loader, the set lives in HBM; a batch is a device-side gather tha
 ``image_gather_nhwc4`` HIP kernel turns straight into the stem's input format: NHWC bf16
 with the 3 channels zero-padded to 4, scaled by 1/255 (ToTensor semantics, no
 normalisation - like the reference's MNIST pipeline).  On the CPU the same data comes
-out as NCHW float for the PyTorch oracle path.
+out as NCHW float for the PyTorch oracle path.  Optionally the gather normalises
+(``DeviceImages(mean=, std=)``) and augments (``DeviceImageLoader(augment=)``: random crop
+with padding or random resized crop, horizontal flip - ``augment.py``) in the same pass,
+through the ``image_gather_aug_nhwc4`` kernel.
 """
 from __future__ import annotations
 
 import torch
 
+from .augment import AugPlan, Augment, affine_table, apply_fp32
 from .sampler import ShardedSampler, steps_per_epoch
 
 
@@ -52,7 +56,7 @@ def synthetic_imagenet_test(n: int, size: int = 224, num_classes: int = 1000, se
 class DeviceImages:
     """uint8 NHWC images + int64 labels resident on one device."""
 
-    def __init__(self, images_u8: torch.Tensor, labels: torch.Tensor, device):
+    def __init__(self, images_u8: torch.Tensor, labels: torch.Tensor, device, mean=None, std=None):
         if images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[3] != 3:
             raise ValueError(f"expected uint8 [N,H,W,3] images, got {images_u8.dtype} {tuple(images_u8.shape)}")
         if labels.shape[0] != images_u8.shape[0]:
@@ -60,20 +64,45 @@ class DeviceImages:
         self.device = torch.device(device)
         self.images_u8 = images_u8.contiguous().to(self.device)
         self.labels = labels.to(torch.int64).to(self.device)
+        # normalisation is a property of the data set: every gather (train, evaluation) applies it
+        self.normalized = mean is not None
+        self.affine = affine_table(mean, std)  # float32 [3, 2] on the host (a kernel argument)
+        self._identity = {}
+
+    def _identity_plan(self, resample: bool = False) -> AugPlan:
+        if resample not in self._identity:
+            n, h, w, _ = self.images_u8.shape
+            self._identity[resample] = AugPlan.identity(n, h, w, resample).to(self.device)
+        return self._identity[resample]
 
     def __len__(self) -> int:
         return self.images_u8.shape[0]
 
-    def gather(self, idx: torch.Tensor):
-        """GPU: ``(bf16 [B,H,W,4] NHWC4, int64 [B])``; CPU: ``(float32 [B,3,H,W], int64 [B])``."""
+    def gather(self, idx: torch.Tensor, plan: AugPlan | None = None):
+        """GPU: ``(bf16 [B,H,W,4] NHWC4, int64 [B])``; CPU: ``(float32 [B,3,H,W], int64 [B])``.
+        ``plan``: the epoch's augmentation table (rows indexed by the data-set index, on this
+        device).  With a plan or a normalisation the augmenting kernel runs, and the CPU returns
+        the values it stores (bf16-rounded; the integer build bit for bit); with neither, the
+        plain gather as before."""
         y = self.labels.index_select(0, idx)
+        augmented = plan is not None or self.normalized
         if self.device.type == "cuda":
             from .. import native
 
             n, h, w, _ = self.images_u8.shape
             out = torch.empty(idx.numel(), h, w, 4, dtype=torch.bfloat16, device=self.device)
-            native.require().image_gather_nhwc4(self.images_u8, idx, out)
+            if augmented:
+                plan = plan if plan is not None else self._identity_plan()
+                native.require().image_gather_aug_nhwc4(self.images_u8, idx, plan.rows, self.affine, out,
+                                                        plan.resample)
+            else:
+                native.require().image_gather_nhwc4(self.images_u8, idx, out)
             return out, y
+        if augmented:
+            plan = plan if plan is not None else self._identity_plan()
+            x = apply_fp32(self.images_u8.index_select(0, idx), plan.rows.index_select(0, idx), self.affine,
+                           plan.resample)
+            return x.permute(0, 3, 1, 2).contiguous(), y
         x = self.images_u8.index_select(0, idx).permute(0, 3, 1, 2).float().div_(255.0)
         return x, y
 
@@ -83,8 +112,8 @@ class DeviceImageLoader:
     batch, drop_last=False), one index upload per epoch."""
 
     def __init__(self, data: DeviceImages, batch_size: int, world_size: int, rank: int,
-                 shuffle: bool = True, seed: int = 0):
-        self.data, self.batch_size = data, int(batch_size)
+                 shuffle: bool = True, seed: int = 0, augment: Augment | None = None):
+        self.data, self.batch_size, self.augment = data, int(batch_size), augment
         self.sampler = ShardedSampler(len(data), world_size, rank, shuffle=shuffle, seed=seed)
 
     def __len__(self) -> int:
@@ -92,5 +121,9 @@ class DeviceImageLoader:
 
     def __iter__(self):
         idx = self.sampler.indices().to(self.data.device, non_blocking=False)
+        plan = None
+        if self.augment is not None:  # the epoch's table, uploaded once with the index list
+            n, h, w, _ = self.data.images_u8.shape
+            plan = self.augment.plan(self.sampler.epoch, n, h, w).to(self.data.device)
         for s in range(0, idx.numel(), self.batch_size):
-            yield self.data.gather(idx[s:s + self.batch_size])
+            yield self.data.gather(idx[s:s + self.batch_size], plan)

@@ -96,6 +96,11 @@ class TrainOptions:
     ema_warmup: bool = False          # decay_k = min(ema_decay, (1 + k) / (10 + k)) for update k
     eval_ema: bool = False            # every evaluation also evaluates the averaged weights
     label_smoothing: float = 0.0      # training loss target (1 - e) onehot + e / C, torch's (0: off; module/CPU path)
+    normalize: bool = False           # resnet18: ImageNet mean/std normalisation in every gather (train and eval)
+    aug_crop_pad: int = 0             # resnet18: random crop with P pixels of black padding (0: off)
+    aug_rrc: bool = False             # resnet18: random resized crop (ratio 3/4..4/3), bilinear
+    aug_scale_min: float = 0.08       # aug_rrc: the smallest area share of the box
+    aug_flip: bool = False            # resnet18: horizontal flip, p = 0.5, after the crop
 
 
 def validate_options(opts: TrainOptions):
@@ -132,6 +137,18 @@ def validate_options(opts: TrainOptions):
         raise ValueError("--eval_ema / --ema_warmup need a weight EMA: set --ema_decay D")
     if not 0.0 <= opts.label_smoothing <= 1.0:
         raise ValueError("--label_smoothing must lie in [0, 1] (0 = off)")
+    if opts.aug_crop_pad < 0:
+        raise ValueError("--aug_crop_pad must be >= 0 (0 = off)")
+    if opts.aug_crop_pad and opts.aug_rrc:
+        raise ValueError("--aug_crop_pad and --aug_rrc are two crop modes: choose one")
+    if opts.aug_crop_pad >= opts.image_size and opts.model == "resnet18":
+        raise ValueError(f"--aug_crop_pad must be smaller than --image_size {opts.image_size}")
+    if not 0.0 < opts.aug_scale_min <= 1.0:
+        raise ValueError("--aug_scale_min must lie in (0, 1]")
+    if opts.model != "resnet18" and uses_augment(opts):
+        raise ValueError("--normalize / --aug_crop_pad / --aug_rrc / --aug_flip run inside the image gather of "
+                         "--model resnet18; simplecnn's MNIST loaders and the fused engine's in-kernel gather "
+                         "have no augmenting build")
     if opts.optimizer == "adamw" and opts.momentum != 0:
         raise ValueError("--momentum is SGD's; --optimizer adamw takes --beta1 / --beta2 / --adam_eps")
     if (opts.device or "").lower() == "gpu":  # the fused engine is certain: refuse before any process starts
@@ -171,6 +188,27 @@ def check_fused_engine_options(opts: TrainOptions, fused: bool):
 
 def uses_lr_schedule(opts: TrainOptions) -> bool:
     return opts.lr_schedule != "none" or opts.warmup_steps > 0
+
+
+def uses_augment(opts: TrainOptions) -> bool:
+    return bool(opts.normalize or opts.aug_crop_pad or opts.aug_rrc or opts.aug_flip)
+
+
+def build_augment(opts: TrainOptions):
+    """The run's Augment from the flags (None: no crop and no flip) - a pure function of the
+    flags and the seed, so every rank and every resumed run draws the same tables."""
+    if not (opts.aug_crop_pad or opts.aug_rrc or opts.aug_flip):
+        return None
+    from ..data.augment import Augment
+
+    return Augment(crop_pad=opts.aug_crop_pad, rrc=opts.aug_rrc, scale=(opts.aug_scale_min, 1.0),
+                   flip=opts.aug_flip, seed=opts.seed or 0)
+
+
+def augment_tag(opts: TrainOptions) -> str:
+    """``rrc+flip+norm``-style summary for the metrics records ('' when everything is off)."""
+    aug = build_augment(opts)
+    return "+".join(([aug.describe()] if aug is not None else []) + (["norm"] if opts.normalize else []))
 
 
 def optimizer_steps_per_epoch(n_batches: int, grad_accum: int = 1, max_steps: int | None = None) -> int:
@@ -236,8 +274,12 @@ def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
     print(f"Rank {rank} model wrapped in DDP", flush=True)
 
     if opts.model == "resnet18":
+        from ..data.augment import IMAGENET_MEAN, IMAGENET_STD
+
+        norm = dict(mean=IMAGENET_MEAN, std=IMAGENET_STD) if opts.normalize else {}
         imgs, labels = synthetic_imagenet(opts.dataset_size, opts.image_size, opts.num_classes)
-        loader = DeviceImageLoader(DeviceImages(imgs, labels, device), batch_size, world_size, rank)
+        loader = DeviceImageLoader(DeviceImages(imgs, labels, device, **norm), batch_size, world_size, rank,
+                                   augment=build_augment(opts))
         sampler = loader.sampler
     elif on_gpu:
         imgs, labels, src = load_mnist(opts.data_root, opts.data)
@@ -251,7 +293,7 @@ def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
     if (opts.eval_every or opts.eval_only) and opts.model == "resnet18":
         timgs, tlabels = synthetic_imagenet_test(opts.eval_size, opts.image_size, opts.num_classes,
                                                  n_train=opts.dataset_size)
-        edata, tsrc = DeviceImages(timgs, tlabels, device), "synthetic"
+        edata, tsrc = DeviceImages(timgs, tlabels, device, **norm), "synthetic"  # evaluation never augments
         if rank == 0:
             print(f"Rank {rank}: Eval split: {tsrc} ({len(edata)} images)", flush=True)
     elif opts.eval_every or opts.eval_only:
@@ -714,6 +756,8 @@ def _record_metrics(opts, rank, ws, epoch, nsteps, batch, dt, samples, ev=None, 
             rec["eval_ema_top5"] = ev_ema.top5
     if opts.label_smoothing:
         rec["label_smoothing"] = opts.label_smoothing
+    if uses_augment(opts):
+        rec["augment"] = augment_tag(opts)
     if ema_updates is not None:
         rec["ema_updates"] = ema_updates
     if clip is not None:

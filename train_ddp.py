@@ -133,6 +133,19 @@ def parse_args(argv=None):
     p.add_argument("--eval_ema", action="store_true",
                    help="every --eval_every / --eval_only evaluation also evaluates the averaged weights "
                         "(an extra 'Eval EMA' line; BatchNorm statistics are the live ones)")
+    p.add_argument("--normalize", action="store_true",
+                   help="resnet18: normalise with the ImageNet mean / std inside every image gather, training "
+                        "and evaluation alike (one fma per value in the gather kernel)")
+    p.add_argument("--aug_crop_pad", type=int, default=0, metavar="P",
+                   help="resnet18: random crop with P pixels of black padding, as torchvision's "
+                        "RandomCrop(size, padding=P), inside the gather kernel (0 = off)")
+    p.add_argument("--aug_rrc", action="store_true",
+                   help="resnet18: random resized crop (area share --aug_scale_min..1, ratio 3/4..4/3, "
+                        "bilinear) back to the stored size, inside the gather kernel; not with --aug_crop_pad")
+    p.add_argument("--aug_scale_min", type=float, default=0.08, metavar="S",
+                   help="aug_rrc: the smallest share of the image area a box takes, in (0, 1]")
+    p.add_argument("--aug_flip", action="store_true",
+                   help="resnet18: horizontal flip with p = 0.5 after the crop, inside the gather kernel")
     return p.parse_args(argv)
 
 
@@ -157,6 +170,8 @@ def main(argv=None):
                         adam_eps=a.adam_eps, trust_coef=a.trust_coef, lars_eps=a.lars_eps,
                         lars_exclude=a.lars_exclude, ema_decay=a.ema_decay, ema_warmup=a.ema_warmup,
                         eval_ema=a.eval_ema, label_smoothing=a.label_smoothing,
+                        normalize=a.normalize, aug_crop_pad=a.aug_crop_pad, aug_rrc=a.aug_rrc,
+                        aug_scale_min=a.aug_scale_min, aug_flip=a.aug_flip,
                         stall=tuple(float(v) for v in a.stall_at.split(":")) if a.stall_at else None,
                         fault=tuple(int(v) for v in a.fault_at.split(":")) if a.fault_at else None)
     validate_options(opts)
