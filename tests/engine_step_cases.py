@@ -1,5 +1,6 @@
-"""One bf16 SimpleCNN engine step, stage by stage and element by element, against float64
-(tests/test_engine_step_elementwise_gpu.py runs the engine through it,
+"""One SimpleCNN engine step - bf16, or exact fp32 (the second table below) - stage by stage and
+element by element, against float64 (tests/test_engine_step_elementwise_gpu.py and
+tests/test_engine_step_fp32_elementwise_gpu.py run the engine through it,
 tests/test_engine_step_bounds_cpu.py shows that it admits a correct step and rejects wrong
 ones).  A helper module, not a test module; it needs no GPU.
 
@@ -63,6 +64,63 @@ carried into the stages that read it (first order in the carried error, exact in
 roundings at the engine's store points, as R.simple_cnn_step_bf16, whose results it must keep
 reproducing) that also returns the intermediates; its keyword arguments plant the wiring
 errors the CPU test wants rejected.
+
+The exact-fp32 step (``prec="fp32"``: engine.cpp launch_step_t<float>;
+tests/test_engine_step_fp32_elementwise_gpu.py).  The operands are the fp32 masters themselves
+(no bf() of w2 / wfc), every store is fp32 (no 2**-8 term), the products round too: every bound
+is acc_bound(n, A, f32_operands=True) = 3 n u A.  The counts, and where they were counted:
+
+  shadows     w2t_f32 ([tap][ci][co], SHADOW_F32_TAPT) and wfc_frag32 (SHADOW_F32_FCFRAG) are, bit
+              for bit, the masters before the step at kernel_bounds.shadow_index
+  a1          never stored (store_a1 = 0: conv1_recompute_tile in the forward's and the wgrad
+              role's staging pass, conv1_eval_g in the dgrad role's mask).  Reference: the float64
+              conv1, e_a1 = 3 * 11 u A (9 fma, the bias, u8 / 255: the per-kernel suite's conv1_fwd row)
+  a2          conv2 of a1 with the master w2, b2: n = 9 * 32 + 1 (conv3x3_fwd_body.inc.h: the
+              16x16x4 MFMA chain tap-major over the 32 channels, the bias add) on |a1| + e_a1, plus
+              the float64 conv of e_a1 with |w2| (first order in the carried error)
+  fc_part     (level 1) per block of CH = 64 pxt_fwd pixels (the fp32 engine resolves pxt_fwd = 2:
+              CH = 128) of the stored a2 against wfc in the wfc_frag32 fragment order (fma chains of
+              4 channels x 4 groups per pixel, sum16 over a tile's pixels, the fixed-order sum of CH /
+              16 tiles x 4 groups): n = 16 + 4 + CH / 4 = 52, the longest chain of roundings between
+              a term and the partial (a lane's 16 fma from 0, sum16's 4 levels, CH / 4 adds) - counted
+              anew from conv3x3_fwd_body.inc.h: the per-kernel suite's 64 CH + CH / 4 counts every term
+              of the block as if summed in one chain, 158 times this bound, and would let a
+              bf16-rounded wfc through
+  dlogits,    as above; stored by the level-3 forward (FwdDz dl_out / loss_rows), carried on
+  loss_rows   level 1.  The end-to-end logit error is 3 n u A, n = HW C + HW / 16 + 1; the fold of
+              stored partials has no products and keeps 2 G u (sum |part| + |bias|)
+  loss_hist   as above
+  dz2         n = 10 (level 3: the forward's fma chain o = 0..9 from 0 over the wfc_frag32 quads it
+              holds; level 1: fc_bwd's dX over the plain master); masked elements (stored a2 <= 0)
+              are exactly 0
+  dz1         never stored: d = the float64 dgrad of the stored dz2 with the master w2 under the
+              float64 conv1 mask, e1 = 3 * 9 * 64 u A where the mask keeps the element, 0 where it
+              drops it (conv3x3_body.h dgrad_body: 9 taps x two 32-wide K steps of 16x16x4 MFMAs; WGS
+              = 1 reads the A fragments from w2t_f32 in global memory, the chain is the same)
+  grad wfc,   n = B + 2 (fc_bwd_body.h fc_dw_wave_chunk / fc_bwd_bias_loss: a fma per image, the
+  grad bfc    scale), as the bf16 table
+  w2slab      row (image, chunk of R rows), R = functional.wgrad_rows(28, max_batch, float32) (4, 2
+              or 1), the rows conv3x3_wgrad_blocks(B, 28, R) counts: n = nslot = roundup32(R
+              roundup8(W)) (wgrad_body F32: every (co, tap, ci) runs one 16x16x4 MFMA chain over
+              the nslot pixel slots) on |dz2| (|a1| + e_a1), plus sum |dz2| e_a1.  wgrad_split = 2
+              puts two blocks on a row, the chain unchanged: half 0 (ciT = 0) writes columns ci <
+              16 of every (co, tap) and the 64 bias columns, half 1 (ciT = 16) the columns ci >= 16
+  w1slab      row = block of CH1 = 64 pxt_dgrad pixels, conv3x3_dgrad_blocks(B, 28, 28, pxt_dgrad)
+              rows: n = CH1 + 9 and the dz1 carry of the bf16 table without its store term.  The
+              dgrad channel split (dgrad_body HALF) puts two blocks on a row: half `by` writes conv1
+              channels [16 by, 16 by + 16) - columns [144 by, 144 by + 144) and bias columns 288 +
+              [16 by, 16 by + 16)
+  grad w1,b1, the float64 row sums under the row bounds summed + reduce_bound; and bit for bit the
+  grad w2,b2  float32 replay_reduce / replay_finish of the STORED rows (stages replay_*), with
+              reduce_groups of the two row counts - slab_reduce.h's order, which grad_reduce and the
+              conv backward's fused reducers share
+  params,     as the bf16 table
+  momentum
+
+The conv1 ReLU mask is recomputed, so it may differ from float64 where the float64
+pre-activation lies inside e_a1 (the ambiguous set): there the carried dz1 bound is the unmasked
+|dgrad| + its accumulation bound, whatever the float64 mask says.  check_step asserts that the
+set holds at most AMBIG_CAP = 1e-4 of a1's elements.
 """
 import functools
 
@@ -85,24 +143,43 @@ SHAPES = {"w1": (C1, 3, 3, 1), "b1": (C1,), "w2": (C2, 3, 3, C1), "b2": (C2,), "
 STAGES = ("shadows", "a1", "a2", "fc_part", "dlogits", "loss_rows", "dlogits_part", "loss_rows_part", "loss_hist",
           "dz2", "dz1", "grad_wfc", "grad_bfc", "w2slab", "grad_w2", "grad_b2", "w1slab", "grad_w1", "grad_b1") + \
     tuple(f"param_{k}" for k in PARAMS) + tuple(f"momentum_{k}" for k in PARAMS)
+# the same order with the fp32 table's bitwise replay of the four reduced gradients in it
+ORDER = tuple(t for s in STAGES for t in ((s, "replay_" + s[5:]) if s in ("grad_w2", "grad_b2", "grad_w1", "grad_b1") else (s,)))
+AMBIG_CAP = 1e-4  # the largest share of a1 whose recomputed ReLU mask may differ from float64's
+
+
+def fp32_stages(level, momentum):
+    """The stages of the fp32 table a step of chain ``level`` (1 or 3) with every gradient stored
+    reports: fc_part where the forward stores it (level 1), dlogits and loss_rows where it
+    stores them (level 3); no a1, no dz1."""
+    s = {"shadows", "a2", "loss_hist", "dz2", "w2slab", "w1slab"} | {f"param_{k}" for k in PARAMS}
+    s |= {"fc_part"} if level < 3 else {"dlogits", "loss_rows"}
+    s |= {f"grad_{k}" for k in PARAMS} | {f"replay_{k}" for k in ("w1", "b1", "w2", "b2")}
+    return s | ({f"momentum_{k}" for k in PARAMS} if momentum else set())
 
 
 def n32(v):
     return float(np.float32(v))
 
 
-def make_plan(B, level=0, pxt_fwd=1, pxt_dgrad=2, wgrad_rows=None, max_batch=None, k=0, lr=0.01, momentum=0.0,
-              dampening=0.0, weight_decay=0.0, nesterov=False, first_step=True, world=1, plain_fc_fresh=None):
+def make_plan(B, level=0, pxt_fwd=None, pxt_dgrad=2, wgrad_rows=None, max_batch=None, k=0, lr=0.01, momentum=0.0,
+              dampening=0.0, weight_decay=0.0, nesterov=False, first_step=True, world=1, plain_fc_fresh=None,
+              prec="bf16"):
     """What check_step needs to know about the chain that ran.  ``k``: the step's index in its
     epoch (its loss_hist slot); ``wgrad_rows``: the engine's R, chosen for ``max_batch``
     (functional.wgrad_rows when None); ``first_step``: the momentum buffer's initialising step;
-    ``plain_fc_fresh``: whether wfc_bf16 is kept current (not on the level-3 chain)."""
+    ``plain_fc_fresh``: whether wfc_bf16 is kept current (not on the level-3 chain); ``prec``:
+    "bf16" or "fp32", the table of the module docstring the step is held to; ``pxt_fwd`` None: 1,
+    for fp32 the 2 its engine resolves."""
+    assert prec in ("bf16", "fp32"), prec
     mb = max_batch or B
+    if pxt_fwd is None:
+        pxt_fwd = 2 if prec == "fp32" else 1
     if wgrad_rows is None:
-        wgrad_rows = next((r for r in (7, 4, 2, 1) if mb * -(-H // r) >= 128), 1)
+        wgrad_rows = next((r for r in ((7, 4, 2, 1) if prec == "bf16" else (4, 2, 1)) if mb * -(-H // r) >= 128), 1)
     return dict(B=B, level=level, CH=64 * pxt_fwd, CH1=64 * pxt_dgrad, R=wgrad_rows, max_batch=mb, k=k, lr=n32(lr),
                 momentum=n32(momentum), dampening=n32(dampening), wd=n32(weight_decay), nesterov=bool(nesterov),
-                first_step=bool(first_step), world=world,
+                first_step=bool(first_step), world=world, prec=prec,
                 plain_fc_fresh=(level < 3) if plain_fc_fresh is None else plain_fc_fresh)
 
 
@@ -132,6 +209,19 @@ def entry_shadows(before):
             "w2t_bf16": shadow_of(before["w2"], K.SHADOW_BF16_TAPT, C2, 9, C1),
             "wfc_frag": shadow_of(before["wfc"], K.SHADOW_BF16_FCFRAG, HW, C2),
             "wfc_bf16": shadow_of(before["wfc"], K.SHADOW_BF16)}
+
+
+def copy_of(master, kind, a=0, b=0, c=0):
+    """The fp32 re-ordered copy of a flat fp32 master in layout ``kind``."""
+    flat = master.detach().cpu().float().reshape(-1)
+    out = torch.zeros(K.shadow_dst_numel(kind, flat.numel()))
+    out[torch.from_numpy(K.shadow_index(kind, flat.numel(), a, b, c))] = flat
+    return out
+
+
+def entry_shadows_fp32(before):
+    return {"w2t_f32": copy_of(before["w2"], K.SHADOW_F32_TAPT, C2, 9, C1),
+            "wfc_frag32": copy_of(before["wfc"], K.SHADOW_F32_FCFRAG, HW, C2)}
 
 
 def nslot(R_):
@@ -210,51 +300,80 @@ def _xent(x, absum, G, labels, gscale):
 
 def check_step(obs, before, x_u8, labels, B, plan):
     """{stage: (largest error / bound, index of the worst element)} for the stages present in
-    ``obs`` (see the module docstring).  ``obs``: CPU tensors by name - the entry shadows, a1, a2,
-    fc_part, dlogits, loss_rows, loss_hist (+ loss_hist_before), dz2, dz1, w2slab, w1slab, grads
-    {name: tensor}, params_after {name: tensor}, momentum_before / momentum_after {name: tensor}.
-    ``before``: the fp32 masters before the step; ``x_u8`` [B,28,28] uint8 and ``labels`` [B]: the
-    step's batch, gathered by the caller from the sampler's index list."""
+    ``obs`` (see the module docstring; plan["prec"] picks the table).  ``obs``: CPU tensors by
+    name - the entry shadows, a1, a2, fc_part, dlogits, loss_rows, loss_hist (+ loss_hist_before),
+    dz2, dz1, w2slab, w1slab, grads {name: tensor}, params_after {name: tensor}, momentum_before /
+    momentum_after {name: tensor}.  ``before``: the fp32 masters before the step; ``x_u8``
+    [B,28,28] uint8 and ``labels`` [B]: the step's batch, gathered by the caller from the
+    sampler's index list."""
     res = {}
     x_u8, labels = x_u8.detach().cpu(), labels.detach().cpu().long()
     assert x_u8.shape == (B, H, W) and labels.shape == (B,)
     P = {k: before[k].detach().cpu().float().reshape(SHAPES[k]) for k in PARAMS}
-    w2b, wfcb = bf(P["w2"]), bf(P["wfc"])
+    f32 = plan.get("prec", "bf16") == "fp32"
+    # the operands: the bf16 shadows' values, or the masters themselves
+    w2o, wfco = (P["w2"], P["wfc"]) if f32 else (bf(P["w2"]), bf(P["wfc"]))
+    stored = (lambda ref, E: E) if f32 else bf16_store_bound  # fp32 stores do not round
+
+    def ab(n, A):
+        return acc_bound(n, A, f32)
+
     scale = n32(1.0 / plan["world"])
     gscale = n32(np.float32(1.0) / np.float32(B))
 
     # ---- shadows at step entry
-    want = entry_shadows(P)
-    sh = [bitwise(obs[k], want[k]) for k in ("w2_bf16", "w2t_bf16", "wfc_frag") if k in obs]
-    if plan["plain_fc_fresh"] and "wfc_bf16" in obs:
-        sh.append(bitwise(obs["wfc_bf16"], want["wfc_bf16"]))
+    if f32:
+        want = entry_shadows_fp32(P)
+        sh = [bitwise(obs[k], want[k]) for k in ("w2t_f32", "wfc_frag32") if k in obs]
+    else:
+        want = entry_shadows(P)
+        sh = [bitwise(obs[k], want[k]) for k in ("w2_bf16", "w2t_bf16", "wfc_frag") if k in obs]
+        if plan["plain_fc_fresh"] and "wfc_bf16" in obs:
+            sh.append(bitwise(obs["wfc_bf16"], want["wfc_bf16"]))
     if sh:
         res["shadows"] = max(sh, key=lambda t: t[0])
 
     # ---- forward
-    a1 = obs["a1"].reshape(-1)[:B * HW * C1].view(B, H, W, C1) if "a1" in obs else None
     a2 = obs["a2"].reshape(-1)[:B * HW * C2].view(B, H, W, C2)
-    if a1 is not None:
-        ref = R.conv1_64(x_u8, P["w1"].reshape(C1, 9), P["b1"])
-        A = R.conv3x3_64((f64(x_u8) / 255.0).unsqueeze(-1), f64(P["w1"]).abs(), f64(P["b1"]).abs())
-        res["a1"] = worst(a1, ref, bf16_store_bound(ref, acc_bound(11, A)))
-    else:  # (a chain that never stores a1: the float64 conv1, rounded as the kernel stores it)
-        a1 = bf(R.conv1_64(x_u8, P["w1"].reshape(C1, 9), P["b1"]))
-    ref = R.conv3x3_64(a1, w2b, P["b2"], True)
-    A = R.conv3x3_64(a1.abs(), w2b.abs(), P["b2"].abs())
-    res["a2"] = worst(a2, ref, bf16_store_bound(ref, acc_bound(9 * C1 + 1, A)))
+    x01 = f64(x_u8) / 255.0
+    A1 = R.conv3x3_64(x01.unsqueeze(-1), f64(P["w1"]).abs(), f64(P["b1"]).abs())
+    if f32:
+        # a1 is never stored: the float64 conv1, its bound e_a1 carried into a2, the w2 slab rows
+        # and (through the recomputed mask's ambiguous set) the carried dz1
+        assert "a1" not in obs and "dz1" not in obs, "the fp32 step stores neither a1 nor dz1"
+        pre = R.conv1_64(x_u8, P["w1"].reshape(C1, 9), P["b1"], relu=False)
+        a1, e_a1 = torch.relu(pre), ab(11, A1)
+        amb = pre.abs() <= e_a1
+        share = amb.double().mean().item()
+        assert share <= AMBIG_CAP, f"{int(amb.sum())} of {amb.numel()} conv1 masks are ambiguous: more than {AMBIG_CAP}"
+        keep1 = pre > 0
+        ref = R.conv3x3_64(a1, w2o, P["b2"], True)
+        A = R.conv3x3_64(a1 + e_a1, w2o.abs(), P["b2"].abs())
+        res["a2"] = worst(a2, ref, ab(9 * C1 + 1, A) + R.conv3x3_64(e_a1, w2o.abs()))
+    else:
+        a1 = obs["a1"].reshape(-1)[:B * HW * C1].view(B, H, W, C1) if "a1" in obs else None
+        if a1 is not None:
+            ref = R.conv1_64(x_u8, P["w1"].reshape(C1, 9), P["b1"])
+            res["a1"] = worst(a1, ref, bf16_store_bound(ref, acc_bound(11, A1)))
+        else:  # (a chain that never stores a1: the float64 conv1, rounded as the kernel stores it)
+            a1 = bf(R.conv1_64(x_u8, P["w1"].reshape(C1, 9), P["b1"]))
+        ref = R.conv3x3_64(a1, w2o, P["b2"], True)
+        A = R.conv3x3_64(a1.abs(), w2o.abs(), P["b2"].abs())
+        res["a2"] = worst(a2, ref, bf16_store_bound(ref, acc_bound(9 * C1 + 1, A)))
+        keep1 = f64(a1) > 0
 
     # ---- logits, cross-entropy
-    xe = R.fc64(a2, wfcb, P["bfc"])
-    Ae = R.fc64(a2.abs(), wfcb.abs(), P["bfc"].abs())
-    dl_ref, rl_ref, bd, bl = _xent(xe, Ae, HW * C2 + HW // 16 + 1, labels, gscale)
+    xe = R.fc64(a2, wfco, P["bfc"])
+    Ae = R.fc64(a2.abs(), wfco.abs(), P["bfc"].abs())
+    # (xent_rows_bounds takes e_l = 2 G u A: the exact-fp32 3 n u A is G = 1.5 n)
+    dl_ref, rl_ref, bd, bl = _xent(xe, Ae, (HW * C2 + HW // 16 + 1) * (1.5 if f32 else 1), labels, gscale)
     if "fc_part" in obs:
         CH = plan["CH"]
         nblk = -(-B * HW // CH)
         part = obs["fc_part"].reshape(-1)[:nblk * 2 * NO].view(nblk, 2, NO)
-        pref = R.fc_block_partials64(a2, wfcb, CH)
-        pA = R.fc_block_partials64(a2.abs(), wfcb.abs(), CH)
-        res["fc_part"] = worst(part, pref, acc_bound(64 * CH + CH // 4, pA))
+        pref = R.fc_block_partials64(a2, wfco, CH)
+        pA = R.fc_block_partials64(a2.abs(), wfco.abs(), CH)
+        res["fc_part"] = worst(part, pref, ab(16 + 4 + CH // 4 if f32 else 64 * CH + CH // 4, pA))
         terms = [fold_terms(b, CH) for b in range(B)]
         p64, b64 = f64(part), f64(P["bfc"])
         xp = torch.stack([sum(p64[k, s] for k, s in terms[b]) + b64 for b in range(B)])
@@ -291,42 +410,62 @@ def check_step(obs, before, x_u8, labels, B, plan):
     # ---- fc backward
     dz2 = obs["dz2"].reshape(-1)[:B * HW * C2].view(B, H, W, C2)
     keep2 = f64(a2) > 0
-    ref, _, _ = R.fc_bwd64(dl64, a2, wfcb, 1.0, True)
-    A, _, _ = R.fc_bwd64(dl64.abs(), a2, wfcb.abs(), 1.0, True)
-    E = acc_bound(NO, A)
+    ref, _, _ = R.fc_bwd64(dl64, a2, wfco, 1.0, True)
+    A, _, _ = R.fc_bwd64(dl64.abs(), a2, wfco.abs(), 1.0, True)
+    E = ab(NO, A)
     if e_d is not None:
-        E = E + R.fc_bwd64(e_d, a2, wfcb.abs(), 1.0, True)[0]
-    res["dz2"] = worst(dz2, ref, bf16_store_bound(ref, E), exact_zero=~keep2)
-    _, gw, gb = R.fc_bwd64(dl64, a2, wfcb, scale, False)
-    _, Aw, Ab = R.fc_bwd64(dl64.abs(), a2.abs(), wfcb, scale, False)
-    Ew, Eb = acc_bound(B + 2, Aw), acc_bound(B + 2, Ab)
+        E = E + R.fc_bwd64(e_d, a2, wfco.abs(), 1.0, True)[0]
+    res["dz2"] = worst(dz2, ref, stored(ref, E), exact_zero=~keep2)
+    _, gw, gb = R.fc_bwd64(dl64, a2, wfco, scale, False)
+    _, Aw, Ab = R.fc_bwd64(dl64.abs(), a2.abs(), wfco, scale, False)
+    Ew, Eb = ab(B + 2, Aw), ab(B + 2, Ab)
     if e_d is not None:
-        _, cw, cb = R.fc_bwd64(e_d, a2.abs(), wfcb, scale, False)
+        _, cw, cb = R.fc_bwd64(e_d, a2.abs(), wfco, scale, False)
         Ew, Eb = Ew + cw, Eb + cb
     gref = {"wfc": (gw, Ew), "bfc": (gb, Eb)}
 
     # ---- conv backward
-    keep1 = f64(a1) > 0
-    d1 = R.conv3x3_dgrad64(dz2, w2b) * keep1
-    E1 = bf16_store_bound(d1, acc_bound(9 * C2, R.conv3x3_dgrad64(dz2.abs(), w2b.abs()) * keep1))
-    x01 = f64(x_u8) / 255.0
     CH1 = plan["CH1"]
-    if "dz1" in obs:
-        dz1 = obs["dz1"].reshape(-1)[:B * HW * C1].view(B, H, W, C1)
-        res["dz1"] = worst(dz1, d1, E1, exact_zero=~keep1)
-        r1 = w1_rows_of(dz1, x01, CH1)
-        E1r = acc_bound(CH1 + 9, w1_rows_of(dz1.abs(), x01, CH1))
-    else:
+    if f32:
+        # dz1 stays in registers (level >= 1) and is fp32: no store term.  An ambiguous mask may go
+        # either way, so there the bound is the whole unmasked value besides its accumulation bound
+        dun = R.conv3x3_dgrad64(dz2, w2o)
+        Ea = ab(9 * C2, R.conv3x3_dgrad64(dz2.abs(), w2o.abs()))
+        d1 = dun * keep1
+        E1 = torch.where(amb, dun.abs() + Ea, Ea * keep1)
         r1 = w1_rows_of(d1, x01, CH1)
-        E1r = acc_bound(CH1 + 9, w1_rows_of(d1.abs() + E1, x01, CH1)) + w1_rows_of(E1, x01, CH1)
-    r2 = wgrad_rows_of(dz2, a1, plan["R"])
-    E2r = acc_bound(nslot(plan["R"]), wgrad_rows_of(dz2.abs(), a1.abs(), plan["R"]))
+        E1r = ab(CH1 + 9, w1_rows_of(d1.abs() + E1, x01, CH1)) + w1_rows_of(E1, x01, CH1)
+        r2 = wgrad_rows_of(dz2, a1, plan["R"])
+        c2 = wgrad_rows_of(dz2.abs(), e_a1, plan["R"])
+        c2[:, N_W2:] = 0.0  # (the bias columns do not read a1)
+        E2r = ab(nslot(plan["R"]), wgrad_rows_of(dz2.abs(), a1 + e_a1, plan["R"])) + c2
+    else:
+        d1 = R.conv3x3_dgrad64(dz2, w2o) * keep1
+        E1 = bf16_store_bound(d1, acc_bound(9 * C2, R.conv3x3_dgrad64(dz2.abs(), w2o.abs()) * keep1))
+        if "dz1" in obs:
+            dz1 = obs["dz1"].reshape(-1)[:B * HW * C1].view(B, H, W, C1)
+            res["dz1"] = worst(dz1, d1, E1, exact_zero=~keep1)
+            r1 = w1_rows_of(dz1, x01, CH1)
+            E1r = acc_bound(CH1 + 9, w1_rows_of(dz1.abs(), x01, CH1))
+        else:
+            r1 = w1_rows_of(d1, x01, CH1)
+            E1r = acc_bound(CH1 + 9, w1_rows_of(d1.abs() + E1, x01, CH1)) + w1_rows_of(E1, x01, CH1)
+        r2 = wgrad_rows_of(dz2, a1, plan["R"])
+        E2r = acc_bound(nslot(plan["R"]), wgrad_rows_of(dz2.abs(), a1.abs(), plan["R"]))
+    grads = obs.get("grads", {})
+    GR = K.reduce_groups([r2.shape[0], r1.shape[0]])
     for name, rows, Er, nw, gw_, gb_ in (("w2slab", r2, E2r, N_W2, "w2", "b2"), ("w1slab", r1, E1r, C1 * 9, "w1", "b1")):
         tot = Er.sum(0)
         if name in obs:
             slab = obs[name].reshape(-1)[:rows.numel()].view(rows.shape)
             res[name] = worst(slab, rows, Er)
             tot = tot + K.reduce_bound(f64(slab), scale)
+            if f32 and torch.isfinite(slab).all():
+                # the reduced gradients are the float32 replay of the stored rows, bit for bit
+                red = torch.from_numpy(K.replay_finish(K.replay_reduce(slab.float().numpy(), GR), scale))
+                for k_, part_ in ((gw_, red[:nw]), (gb_, red[nw:])):
+                    if k_ in grads:
+                        res[f"replay_{k_}"] = bitwise(grads[k_].reshape(-1).float(), part_)
         else:
             tot = tot + K.reduce_bound(rows.abs() + Er, scale)
         g = scale * rows.sum(0)
@@ -334,7 +473,6 @@ def check_step(obs, before, x_u8, labels, B, plan):
         gref[gb_] = (g[nw:], scale * tot[nw:])
 
     # ---- the gradients in the flat buffer, the optimizer
-    grads = obs.get("grads", {})
     for k in PARAMS:
         if k in grads:
             res[f"grad_{k}"] = worst(grads[k].reshape(SHAPES[k]), gref[k][0].reshape(SHAPES[k]), gref[k][1].reshape(SHAPES[k]))
@@ -365,11 +503,11 @@ def check_step(obs, before, x_u8, labels, B, plan):
 
 def failing(res):
     """The stages out of bound, in dependency order."""
-    return [s for s in STAGES if s in res and not res[s][0] <= 1.0]
+    return [s for s in ORDER if s in res and not res[s][0] <= 1.0]
 
 
 def report(res, chain, B, tag="STEP_RATIO"):
-    for s in STAGES:
+    for s in ORDER:
         if s in res:
             print(f"{tag} {chain} {B} {s} {res[s][0]:.3e}")
 
@@ -388,7 +526,7 @@ def _sgd32(p, g, m, a, first):
 
 
 def emulate_step(before, x_u8, labels, B, plan=None, momentum_before=None, loss_hist_before=None,
-                 drop_image=None, gscale=None, drop_w2_row=None, hist_slot=None):
+                 drop_image=None, gscale=None, drop_w2_row=None, hist_slot=None, **fp32_errors):
     """An fp32 / bf16 model of the engine's stage outputs for the batch (x_u8 [B,28,28], labels
     [B]) from the masters ``before``: the ``obs`` of :func:`check_step`, every stage present
     (level 0 with the gradients stored and the optimizer applied).
@@ -398,6 +536,10 @@ def emulate_step(before, x_u8, labels, B, plan=None, momentum_before=None, loss_
     ``drop_w2_row`` - a conv2 slab row the reduction skips; ``hist_slot`` - the loss written to
     another slot than plan["k"]."""
     plan = plan or make_plan(B)
+    if plan.get("prec", "bf16") == "fp32":
+        return _emulate_fp32(before, x_u8, labels, B, plan, momentum_before, loss_hist_before, drop_image, gscale,
+                             drop_w2_row, hist_slot, **fp32_errors)
+    assert not fp32_errors, sorted(fp32_errors)
     P = {k: before[k].detach().cpu().float().reshape(SHAPES[k]) for k in PARAMS}
     x_u8, labels = x_u8.detach().cpu(), labels.detach().cpu().long()
     x = x_u8.float() / 255.0
@@ -462,6 +604,115 @@ def emulate_step(before, x_u8, labels, B, plan=None, momentum_before=None, loss_
         if buf is not None:
             obs["momentum_after"][k] = buf
     return obs
+
+
+def _emulate_fp32(before, x_u8, labels, B, plan, momentum_before=None, loss_hist_before=None, drop_image=None,
+                  gscale=None, drop_w2_row=None, hist_slot=None, bf16_w2=False, bf16_wfc=False, w2t=None,
+                  zero_w2_half=None, borrow_w2_half=None, swap_w1_halves=None, flip_mask=None):
+    """emulate_step for plan["prec"] == "fp32": torch's float32 operators on the masters, no bf16
+    rounding anywhere, a1 and dz1 left out of ``obs`` (the step never stores them); fc_part,
+    dlogits and loss_rows are all present - :func:`stored_on` keeps a chain's set.
+
+    Planted errors besides emulate_step's: ``bf16_w2`` / ``bf16_wfc`` - the weight rounded to
+    bf16 wherever a kernel reads it (a bf16 build wired into the fp32 chain; the copies keep the
+    master's bits); ``w2t`` - "plain": w2t_f32 left in the master's OHWI order, or a masters dict:
+    w2t_f32 derived from those (a step stale) - the dgrad reads what the copy holds;
+    ``zero_w2_half`` / ``borrow_w2_half`` - the ci 16..31 columns of that w2slab row zeroed / taken
+    from the row after it (the one before the last row); ``swap_w1_halves`` - the two conv1-channel
+    halves of that w1slab row exchanged; ``flip_mask`` - the recomputed conv1 ReLU mask of one
+    element (b, h, w, c) inverted in the dgrad role."""
+    P = {k: before[k].detach().cpu().float().reshape(SHAPES[k]) for k in PARAMS}
+    x_u8, labels = x_u8.detach().cpu(), labels.detach().cpu().long()
+    x = x_u8.float() / 255.0
+    obs = dict(entry_shadows_fp32(P))
+    if isinstance(w2t, dict):
+        obs["w2t_f32"] = entry_shadows_fp32(w2t)["w2t_f32"]
+    elif w2t == "plain":
+        obs["w2t_f32"] = P["w2"].reshape(-1).clone()
+    else:
+        assert w2t is None, w2t
+    w2, wfc = (R.bf16r(P["w2"]) if bf16_w2 else P["w2"]), (R.bf16r(P["wfc"]) if bf16_wfc else P["wfc"])
+    # the data gradient's operand is the [tap][ci][co] copy
+    w2d = obs["w2t_f32"][torch.from_numpy(K.shadow_index(K.SHADOW_F32_TAPT, N_W2, C2, 9, C1))].view(SHAPES["w2"])
+    w2d = R.bf16r(w2d) if bf16_w2 else w2d
+    a1 = R.conv1_relu(x, P["w1"], P["b1"])
+    a2 = R.conv3x3(a1, w2, P["b2"], relu=True)
+    obs["a2"] = a2
+    CH = plan["CH"]
+    nblk = -(-B * HW // CH)
+    per_px = torch.einsum("bpc,opc->bpo", a2.reshape(B, HW, C2), wfc)
+    part = torch.zeros(nblk, 2, NO)
+    for k in range(nblk):
+        p0, p1 = k * CH, min((k + 1) * CH, B * HW)
+        n0 = p0 // HW
+        for slot in (0, 1):
+            lo, hi = max(p0, (n0 + slot) * HW), min(p1, (n0 + slot + 1) * HW)
+            if lo < hi:
+                part[k, slot] = per_px[n0 + slot, lo - (n0 + slot) * HW:hi - (n0 + slot) * HW].sum(0)
+    obs["fc_part"] = part
+    logits = torch.stack([sum((part[k, s] for k, s in fold_terms(b, CH)), torch.zeros(NO)) + P["bfc"] for b in range(B)])
+    lp = torch.log_softmax(logits, 1)
+    rows = -lp[torch.arange(B), labels]
+    d = lp.exp()
+    d[torch.arange(B), labels] -= 1.0
+    dl = d * np.float32(np.float32(1.0) / np.float32(B) if gscale is None else gscale)
+    obs["dlogits"], obs["loss_rows"] = dl, rows
+    hist = torch.zeros(plan["k"] + 3) if loss_hist_before is None else loss_hist_before.clone().float()
+    obs["loss_hist_before"] = hist.clone()
+    hist[plan["k"] if hist_slot is None else hist_slot] = rows.sum() / np.float32(B)
+    obs["loss_hist"] = hist
+    dz2 = (dl @ wfc.reshape(NO, -1)).view_as(a2) * (a2 > 0)
+    obs["dz2"] = dz2
+    mask1 = a1 > 0
+    if flip_mask is not None:
+        mask1[tuple(flip_mask)] = ~mask1[tuple(flip_mask)]
+    dz1 = R.conv3x3_dgrad(dz2, w2d) * mask1
+    live = torch.ones(B, dtype=torch.bool)
+    if drop_image is not None:
+        live[drop_image] = False
+    s = np.float32(1.0 / plan["world"])
+    g = {"wfc": ((dl[live].t() @ a2.reshape(B, -1)[live]) * s).view(SHAPES["wfc"]), "bfc": dl[live].sum(0) * s}
+    nRC = -(-H // plan["R"])
+    w2slab = wgrad_rows_of(dz2, a1, plan["R"], torch.float32)
+    w1slab = w1_rows_of(dz1, x, plan["CH1"], torch.float32)
+    hi2 = (torch.arange(N_W2) % C1 >= 16).nonzero().reshape(-1)  # the ci 16..31 columns: the second block's
+    if zero_w2_half is not None:
+        w2slab[zero_w2_half, hi2] = 0.0
+    if borrow_w2_half is not None:
+        other = borrow_w2_half + 1 if borrow_w2_half + 1 < w2slab.shape[0] else borrow_w2_half - 1
+        w2slab[borrow_w2_half, hi2] = w2slab[other, hi2]
+    if swap_w1_halves is not None:
+        r = w1slab[swap_w1_halves].clone()
+        w1slab[swap_w1_halves] = torch.cat([r[144:288], r[:144], r[304:320], r[288:304]])
+    obs["w2slab"], obs["w1slab"] = w2slab, w1slab
+    use2 = live.repeat_interleave(nRC)
+    if drop_w2_row is not None:
+        use2[drop_w2_row] = False
+    r1 = w1slab if drop_image is None else w1_rows_of(dz1 * live.view(B, 1, 1, 1), x, plan["CH1"], torch.float32)
+    GR = K.reduce_groups([w2slab.shape[0], w1slab.shape[0]])
+    # (a skipped row adds +0.0f in its place: the other rows keep their groups)
+    red2 = torch.from_numpy(K.replay_finish(K.replay_reduce((w2slab * use2.view(-1, 1)).numpy(), GR), s))
+    red1 = torch.from_numpy(K.replay_finish(K.replay_reduce(r1.numpy(), GR), s))
+    g.update(w2=red2[:N_W2].view(SHAPES["w2"]), b2=red2[N_W2:], w1=red1[:C1 * 9].view(SHAPES["w1"]), b1=red1[C1 * 9:])
+    obs["grads"] = g
+    a = dict(lr=plan["lr"], momentum=plan["momentum"], dampening=plan["dampening"], wd=plan["wd"], nesterov=plan["nesterov"])
+    obs["params_after"], obs["momentum_after"] = {}, {}
+    if momentum_before is not None:
+        obs["momentum_before"] = {k: momentum_before[k].detach().cpu().float().reshape(SHAPES[k]) for k in PARAMS}
+    for k in PARAMS:
+        m0 = obs["momentum_before"][k] if (plan["momentum"] and not plan["first_step"]) else None
+        pn, buf = _sgd32(P[k], g[k].reshape(SHAPES[k]), m0, a, plan["first_step"])
+        obs["params_after"][k] = pn
+        if buf is not None:
+            obs["momentum_after"][k] = buf
+    return obs
+
+
+def stored_on(obs, level):
+    """``obs`` without what the fp32 chain ``level`` keeps on chip: level 1 the dL rows and the row
+    losses (fc_bwd's prologue), level 3 the partial logits (handed over as granules)."""
+    drop = ("fc_part",) if level >= 3 else ("dlogits", "loss_rows")
+    return {k: v for k, v in obs.items() if k not in drop}
 
 
 # -------------------------------------------------------------------------------- the inputs

@@ -10,6 +10,14 @@ list).  Evidence about the bounds and the checker, not about the engine.
 Rejects: from that emulation, eight planted errors of the kind launch_step_t's wiring can make;
 each must fail, and the first stage to fail (in dependency order) must be the one the error
 belongs to.  A case only counts because the unmodified emulation passes the same check.
+
+The second half does the same for the exact-fp32 table (``prec="fp32"``,
+tests/test_engine_step_fp32_elementwise_gpu.py): the fp32 emulation is admitted at the same sizes
+on both stored-stage sets (level 1, level 3); the wiring errors above, a bf16-rounded weight, a
+wrong w2t_f32, a wrong channel half of a slab row, a conv1 mask flipped outside the ambiguous
+set and a reduced gradient one ulp off the replay are rejected at their stages; a mask flipped
+inside the ambiguous set is admitted; and the ambiguous share stays under its cap for every
+batch the GPU file gathers.
 """
 import functools
 
@@ -175,3 +183,179 @@ def test_carried_bounds_admit_the_chains_that_store_less():
     bad_obs = E.emulate_step(before, x, y, 3, plan, gscale=1.0 / 4)
     less = {k: v for k, v in bad_obs.items() if k not in ("dz1", "dlogits", "loss_rows")}
     assert E.failing(E.check_step(less, before, x, y, 3, plan))[0] == "dz2"
+
+
+# ------------------------------------------------------------------ the exact-fp32 table
+# The same for prec="fp32" (tests/test_engine_step_fp32_elementwise_gpu.py): the emulation has
+# no bf16 rounding and leaves a1 and dz1 out; every bound is 3 n u A.
+@functools.lru_cache(maxsize=None)
+def base32(B, max_batch=None, k=0, momentum=0.0, wd=0.0):
+    """(before, x_u8, labels, plan, obs) of a correct emulated fp32 step.  Shared: do not write."""
+    imgs, labels, perm = E.dataset()
+    mb = max_batch or B
+    idx = perm[k * mb:k * mb + B]
+    plan = E.make_plan(B, level=3, max_batch=mb, k=k, momentum=momentum, weight_decay=wd, first_step=k == 0, prec="fp32")
+    before = E.masters()
+    mom = {n: torch.randn(E.SHAPES[n], generator=torch.Generator().manual_seed(5)) * 0.01 for n in E.PARAMS} if k else None
+    hist = torch.rand(k + 3) if k else None
+    obs = E.emulate_step(before, imgs[idx], labels[idx], B, plan, momentum_before=mom, loss_hist_before=hist)
+    return before, imgs[idx], labels[idx], plan, obs
+
+
+@pytest.mark.parametrize("level", [1, 3])
+@pytest.mark.parametrize("B,max_batch,k,momentum,wd", [(1, None, 0, 0.0, 0.0), (3, None, 0, 0.9, 1e-4), (20, None, 0, 0.0, 0.0),
+                                                       (32, None, 0, 0.9, 1e-4), (8, 64, 0, 0.0, 0.0), (3, None, 2, 0.9, 1e-4)])
+def test_fp32_checker_admits_the_emulated_step(B, max_batch, k, momentum, wd, level):
+    before, x, y, plan, obs = base32(B, max_batch, k, momentum, wd)
+    assert plan["CH"] == 128 and plan["R"] == {1: 1, 3: 1, 20: 4, 32: 4, 8: 4}[B]
+    assert "a1" not in obs and "dz1" not in obs and obs["a2"].dtype == torch.float32
+    res = E.check_step(E.stored_on(obs, level), before, x, y, B, plan)
+    E.report(res, f"cpu_emulation_fp32_l{level}", B, tag="CPU_STEP_RATIO")
+    assert_passes(res, f"fp32 emulation B={B} level {level}")
+    assert set(res) == E.fp32_stages(level, momentum)  # every stage of the fp32 table ran
+
+
+def first32(level, B=3, max_batch=None, **errors):
+    before, x, y, plan, _ = base32(B, max_batch)
+    obs = E.stored_on(E.emulate_step(before, x, y, B, plan, **errors), level)
+    return first_failure(obs, before, x, y, B, plan)
+
+
+def test_fp32_rejects_the_wiring_errors_of_the_bf16_table():
+    first, bad = first32(3, drop_image=1)
+    assert first == "grad_wfc" and {"grad_wfc", "grad_bfc", "grad_w2", "grad_b2", "grad_w1", "grad_b1"} <= set(bad), bad
+    assert not {"a2", "dlogits", "dz2", "w2slab", "w1slab"} & set(bad), bad
+    first, bad = first32(3, gscale=1.0 / 4)
+    assert first == "dlogits" and not {"dz2", "grad_wfc", "grad_w2", "grad_w1"} & set(bad), bad
+    assert first32(1, gscale=1.0 / 4)[0] == "dz2"  # (level 1 carries dL: seen where it is first stored)
+    first, bad = first32(3, B=20, drop_w2_row=20 * 7 - 1)
+    assert first == "grad_w2" and "w2slab" not in bad and "grad_w1" not in bad, bad
+    before, x, y, plan, _ = base32(3, None, 2, 0.9, 1e-4)
+    mom = {n: torch.zeros(E.SHAPES[n]) for n in E.PARAMS}
+    obs = E.emulate_step(before, x, y, 3, plan, momentum_before=mom, loss_hist_before=torch.rand(5), hist_slot=3)
+    first, bad = first_failure(E.stored_on(obs, 3), before, x, y, 3, plan)
+    assert first == "loss_hist" and bad == ["loss_hist"], bad
+
+
+def test_fp32_rejects_the_full_batch_scale_on_a_ragged_tail():
+    first, bad = first32(3, B=8, max_batch=64, gscale=1.0 / 64)
+    assert first == "dlogits" and not {"dz2", "grad_wfc", "grad_w2", "grad_w1"} & set(bad), bad
+
+
+def test_fp32_bounds_are_tighter_than_a_bf16_rounding_of_the_weights():
+    """A bf16 build wired into the fp32 chain: conv2's weight rounded to bf16 fails at a2, the fc
+    weight at the first stored stage that reads it - the partial logits on level 1; on level 3,
+    which stores no partials, dZ2 (a whole logit's 50176 rounded terms average out far below
+    any worst-case bound of their sum; dZ2's 10 do not)."""
+    for level in (1, 3):
+        first, bad = first32(level, bf16_w2=True)
+        assert first == "a2", bad
+    first, bad = first32(1, bf16_wfc=True)
+    assert first == "fc_part" and "a2" not in bad, bad
+    first, bad = first32(3, bf16_wfc=True)
+    assert first == "dz2" and "a2" not in bad, bad
+
+
+def test_fp32_rejects_a_wrong_conv2_weight_copy():
+    first, bad = first32(3, w2t="plain")
+    assert first == "shadows" and "w1slab" in bad and "a2" not in bad, bad  # (the dgrad read it)
+    before0, x, y, plan, obs0 = base32(3)
+    after0 = obs0["params_after"]
+    plan1 = dict(plan, k=1)
+    obs = E.emulate_step(after0, x, y, 3, plan1)
+    assert_passes(E.check_step(E.stored_on(obs, 3), after0, x, y, 3, plan1), "second step")
+    stale = E.stored_on(E.emulate_step(after0, x, y, 3, plan1, w2t=before0), 3)
+    assert not torch.equal(E.bits(stale["w2t_f32"]), E.bits(obs["w2t_f32"]))
+    first, bad = first_failure(stale, after0, x, y, 3, plan1)
+    assert first == "shadows", bad
+
+
+@pytest.mark.parametrize("error", ["zero_w2_half", "borrow_w2_half"])
+def test_fp32_rejects_a_wrong_channel_half_of_a_conv2_slab_row(error):
+    """The second block of a row (ci 16..31) did not write, or wrote the row next to its own."""
+    before, x, y, plan, obs = base32(3)
+    first, bad = first32(3, **{error: 40})
+    assert first == "w2slab" and "w1slab" not in bad, bad
+    res = E.check_step(E.stored_on(E.emulate_step(before, x, y, 3, plan, **{error: 40}), 3), before, x, y, 3, plan)
+    assert res["w2slab"][1][0] == 40 and res["w2slab"][1][1] % E.C1 >= 16 and res["w2slab"][1][1] < E.N_W2, res["w2slab"]
+    # the reduced gradient is still the replay of the rows that were stored
+    assert res["replay_w2"][0] == 0.0 and res["grad_w2"][0] > 1.0
+
+
+def test_fp32_rejects_the_conv1_channel_halves_of_a_w1_slab_row_swapped():
+    first, bad = first32(3, swap_w1_halves=5)
+    assert first == "w1slab" and "w2slab" not in bad, bad
+
+
+def test_fp32_rejects_a_reduced_gradient_one_ulp_off_the_replay():
+    before, x, y, plan, obs = base32(3)
+    off = dict(E.stored_on(obs, 3), grads=dict(obs["grads"]))
+    off["grads"]["b1"] = obs["grads"]["b1"].clone()
+    off["grads"]["b1"][7] = torch.nextafter(off["grads"]["b1"][7], torch.tensor(float("inf")))
+    res = E.check_step(off, before, x, y, 3, plan)
+    assert E.failing(res) == ["replay_b1"], E.failing(res)
+
+
+def _ambiguous_case():
+    """Masters whose b1[5] is moved so that one conv1 pre-activation is (to the rounding of b1
+    itself, within e_a1) zero: an ambiguous element exists."""
+    before, x, y, plan, _ = base32(3)
+    pre = R.conv1_64(x, before["w1"].reshape(E.C1, 9), before["b1"], relu=False)
+    nz = torch.nonzero((x[1] > 0) & (pre[1, :, :, 5] != before["b1"][5].double()))
+    h, w = (int(v) for v in nz[len(nz) // 2])
+    moved = dict(before, b1=before["b1"].clone())
+    moved["b1"][5] = (before["b1"][5].double() - pre[1, h, w, 5]).float()
+    return moved, x, y, plan, (1, h, w, 5)
+
+
+def test_fp32_conv1_mask_flip_passes_inside_the_ambiguous_set_and_fails_outside_it():
+    moved, x, y, plan, at = _ambiguous_case()
+    pre = R.conv1_64(x, moved["w1"].reshape(E.C1, 9), moved["b1"], relu=False)
+    A = R.conv3x3_64((x.double() / 255.0).unsqueeze(-1), moved["w1"].double().abs(), moved["b1"].double().abs())
+    amb = pre.abs() <= E.acc_bound(11, A, True)
+    assert bool(amb[at]) and amb.double().mean().item() <= E.AMBIG_CAP
+    ok = E.stored_on(E.emulate_step(moved, x, y, 3, plan), 3)
+    assert_passes(E.check_step(ok, moved, x, y, 3, plan), "moved bias")
+    inside = E.stored_on(E.emulate_step(moved, x, y, 3, plan, flip_mask=at), 3)
+    assert not torch.equal(inside["w1slab"], ok["w1slab"])  # (the flip changed a row)
+    assert_passes(E.check_step(inside, moved, x, y, 3, plan), "a mask flipped inside the ambiguous set")
+    # outside: the element of the same image and channel with the largest data gradient
+    d = R.conv3x3_dgrad64(ok["dz2"], moved["w2"])[1, :, :, 5].abs() * ~amb[1, :, :, 5]
+    h, w = divmod(int(d.reshape(-1).argmax()), E.W)
+    outside = E.stored_on(E.emulate_step(moved, x, y, 3, plan, flip_mask=(1, h, w, 5)), 3)
+    first, bad = first_failure(outside, moved, x, y, 3, plan)
+    assert first == "w1slab" and "w2slab" not in bad, bad
+
+
+def test_fp32_checker_refuses_more_ambiguous_masks_than_the_cap():
+    before, x, y, plan, obs = base32(3)
+    zeroed = dict(before, w1=torch.zeros_like(before["w1"]), b1=torch.zeros_like(before["b1"]))  # every pre-activation 0
+    with pytest.raises(AssertionError, match="ambiguous"):
+        E.check_step(E.stored_on(obs, 3), zeroed, x, y, 3, plan)
+
+
+# the (n, B, max_batch, epoch, k) of every batch tests/test_engine_step_fp32_elementwise_gpu.py checks
+GPU_BATCHES = [(256, B, B, 0, 0) for B in (1, 12, 20, 32, 40, 64)] + [(256, 32, 32, 0, 3), (256, 32, 32, 0, 6),
+                                                                      (100, 4, 32, 0, 3), (100, 32, 32, 1, 0)]
+
+
+@pytest.mark.parametrize("n,B,max_batch,epoch,k", GPU_BATCHES)
+def test_fp32_ambiguous_masks_stay_under_the_cap_for_every_gpu_batch(n, B, max_batch, epoch, k):
+    """The seed-0 model's conv1 on the window of the sampler's index list the GPU case gathers."""
+    from ddp_amd.data import synthetic_mnist
+    from ddp_amd.data.sampler import ShardedSampler
+    from ddp_amd.models import SimpleCNN
+
+    torch.manual_seed(0)
+    m = SimpleCNN(compute_dtype=torch.float32)
+    imgs, _ = synthetic_mnist(n)
+    sampler = ShardedSampler(n, 1, 0, shuffle=True, seed=0)
+    sampler.set_epoch(epoch)
+    x = imgs[sampler.indices()[k * max_batch:k * max_batch + B]]
+    assert x.shape == (B, 28, 28) and x.dtype == torch.uint8
+    w1, b1 = m.net[0].weight.detach(), m.net[0].bias.detach()
+    pre = R.conv1_64(x, w1.reshape(E.C1, 9), b1, relu=False)
+    A = R.conv3x3_64((x.double() / 255.0).unsqueeze(-1), w1.double().abs().reshape(E.C1, 3, 3, 1), b1.double().abs())
+    share = (pre.abs() <= E.acc_bound(11, A, True)).double().mean().item()
+    print(f"AMBIGUOUS n={n} B={B} epoch={epoch} k={k} share {share:.2e}")
+    assert share <= E.AMBIG_CAP

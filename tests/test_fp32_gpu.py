@@ -3,7 +3,8 @@
 against a float64 PyTorch reference of the same op at <= 1e-5 relative error, the
 module-path SimpleCNN against the stock fp32 model (the reference's nn.Conv2d / nn.Linear,
 /root/reference/model.py:8-16) at <= 1e-4, and the fp32 fused engine's step against the
-float64 oracle ``simple_cnn_step_exact``."""
+float64 oracle ``simple_cnn_step_exact``.  (The engine step per element and stage, with
+a-priori bounds instead of norms: tests/test_engine_step_fp32_elementwise_gpu.py.)"""
 import pytest
 import torch
 
