@@ -128,11 +128,12 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+import elementwise as EW
 from ddp_amd.ops import kernel_bounds as K
 from ddp_amd.ops import reference as R
-from ddp_amd.ops.kernel_bounds import U, acc_bound, bf16_store_bound
+from ddp_amd.ops.kernel_bounds import acc_bound, bf16_store_bound
+from elementwise import BF, bf, bits, bitwise, f64, n32, worst  # noqa: F401  (reachable as E.worst, E.bits ...)
 
-BF = torch.bfloat16
 H = W = 28
 HW, C1, C2, NO = H * W, 32, 64, 10
 N_W2, N_FC = C2 * 9 * C1, NO * HW * C2
@@ -146,6 +147,8 @@ STAGES = ("shadows", "a1", "a2", "fc_part", "dlogits", "loss_rows", "dlogits_par
 # the same order with the fp32 table's bitwise replay of the four reduced gradients in it
 ORDER = tuple(t for s in STAGES for t in ((s, "replay_" + s[5:]) if s in ("grad_w2", "grad_b2", "grad_w1", "grad_b1") else (s,)))
 AMBIG_CAP = 1e-4  # the largest share of a1 whose recomputed ReLU mask may differ from float64's
+failing = functools.partial(EW.failing, order=ORDER)                  # failing(res)
+report = functools.partial(EW.report, order=ORDER, tag="STEP_RATIO")  # report(res, chain, B)
 
 
 def fp32_stages(level, momentum):
@@ -156,10 +159,6 @@ def fp32_stages(level, momentum):
     s |= {"fc_part"} if level < 3 else {"dlogits", "loss_rows"}
     s |= {f"grad_{k}" for k in PARAMS} | {f"replay_{k}" for k in ("w1", "b1", "w2", "b2")}
     return s | ({f"momentum_{k}" for k in PARAMS} if momentum else set())
-
-
-def n32(v):
-    return float(np.float32(v))
 
 
 def make_plan(B, level=0, pxt_fwd=None, pxt_dgrad=2, wgrad_rows=None, max_batch=None, k=0, lr=0.01, momentum=0.0,
@@ -181,19 +180,6 @@ def make_plan(B, level=0, pxt_fwd=None, pxt_dgrad=2, wgrad_rows=None, max_batch=
                 momentum=n32(momentum), dampening=n32(dampening), wd=n32(weight_decay), nesterov=bool(nesterov),
                 first_step=bool(first_step), world=world, prec=prec,
                 plain_fc_fresh=(level < 3) if plain_fc_fresh is None else plain_fc_fresh)
-
-
-def f64(t):
-    return t.detach().cpu().double()
-
-
-def bits(t):
-    t = t.detach().cpu().contiguous()
-    return t.view(torch.int16 if t.dtype == BF else torch.int32)
-
-
-def bf(t):
-    return t.detach().cpu().float().to(BF)
 
 
 def shadow_of(master, kind, a=0, b=0, c=0):
@@ -224,24 +210,31 @@ def entry_shadows_fp32(before):
             "wfc_frag32": copy_of(before["wfc"], K.SHADOW_F32_FCFRAG, HW, C2)}
 
 
+def wgrad_nslot(W_, R_):
+    """The pixel slots conv3x3_wgrad's MFMA chain runs over for R_ rows of width W_: roundup32(R roundup8(W))."""
+    return (R_ * ((W_ + 7) & ~7) + 31) // 32 * 32
+
+
 def nslot(R_):
-    return (R_ * ((W + 7) & ~7) + 31) // 32 * 32
+    return wgrad_nslot(W, R_)
 
 
 def wgrad_rows_of(dy, x, R_, dtype=torch.float64):
-    """conv3x3_wgrad's slab rows [B * ceil(H / R)][Co * 9 * Ci + Co] in ``dtype``: row = image n,
-    chunk c of R output rows - (dW OHWI, db) of those rows alone."""
+    """conv3x3_wgrad's slab rows [B * ceil(H / R)][Co * 9 * Ci + Co] in ``dtype`` for dy [B,H,W,Co]
+    and x [B,H,W,Ci] of any geometry: row = image n, chunk c of R output rows - (dW OHWI, db) of
+    those rows alone."""
     dy, x = dy.detach().cpu().to(dtype), x.detach().cpu().to(dtype)
-    B = dy.shape[0]
-    nRC = -(-H // R_)
+    B, Hh, _, Co = dy.shape
+    nw = Co * 9 * x.shape[3]
+    nRC = -(-Hh // R_)
     sh = [R._shift(x, kh - 1, kw - 1) for kh in range(3) for kw in range(3)]
-    rows = torch.zeros(B, nRC, N_W2 + C2, dtype=dtype)
+    rows = torch.zeros(B, nRC, nw + Co, dtype=dtype)
     for c in range(nRC):
-        r0, r1 = c * R_, min(H, (c + 1) * R_)
+        r0, r1 = c * R_, min(Hh, (c + 1) * R_)
         d = dy[:, r0:r1]
         dw = torch.stack([torch.einsum("nhwo,nhwi->noi", d, s[:, r0:r1]) for s in sh], 2)  # [B,Co,9,Ci]
-        rows[:, c, :N_W2] = dw.reshape(B, -1)
-        rows[:, c, N_W2:] = d.sum(dim=(1, 2))
+        rows[:, c, :nw] = dw.reshape(B, -1)
+        rows[:, c, nw:] = d.sum(dim=(1, 2))
     return rows.reshape(B * nRC, -1)
 
 
@@ -260,35 +253,12 @@ def w1_rows_of(dz, x01, CH1, dtype=torch.float64):
     return torch.cat([dw, d.sum(1)], 1)
 
 
-def fold_terms(b, CH):
-    """(block, slot) of every partial summed into image b's logits (common.h xent_logit_idx)."""
-    p0 = b * HW
-    kb0, kb1 = p0 // CH, (p0 + HW - 1) // CH
+def fold_terms(b, CH, HW_=HW):
+    """(block, slot) of every partial summed into image b's logits (common.h xent_logit_idx), for
+    images of HW_ pixels in blocks of CH."""
+    p0 = b * HW_
+    kb0, kb1 = p0 // CH, (p0 + HW_ - 1) // CH
     return [(kb0 + j, (0 if kb0 * CH == p0 else 1) if j == 0 else 0) for j in range(kb1 - kb0 + 1)]
-
-
-def worst(out, ref, bound, exact_zero=None):
-    """(max |out - ref| / bound, index of the worst element); a non-finite output or a non-zero
-    element under ``exact_zero`` counts as infinitely far out."""
-    o = f64(out)
-    assert o.shape == ref.shape, (o.shape, ref.shape)
-    rr = (o - ref).abs() / (bound + 1e-300)
-    rr = torch.where(torch.isfinite(o), rr, torch.full_like(rr, float("inf")))
-    if exact_zero is not None:
-        rr = torch.where(exact_zero & (o != 0), torch.full_like(rr, float("inf")), rr)
-    if rr.numel() == 0:
-        return 0.0, ()
-    i = int(rr.reshape(-1).argmax())
-    return rr.reshape(-1)[i].item(), tuple(int(v) for v in np.unravel_index(i, tuple(rr.shape)))
-
-
-def bitwise(out, want):
-    """(0 or inf, first differing index): a stage that must match bit for bit."""
-    a, b = bits(out).reshape(-1), bits(want).reshape(-1)
-    if a.shape != b.shape:
-        return float("inf"), ()
-    d = torch.nonzero(a != b)
-    return (0.0, ()) if d.numel() == 0 else (float("inf"), (int(d[0]),))
 
 
 def _xent(x, absum, G, labels, gscale):
@@ -324,12 +294,12 @@ def check_step(obs, before, x_u8, labels, B, plan):
     # ---- shadows at step entry
     if f32:
         want = entry_shadows_fp32(P)
-        sh = [bitwise(obs[k], want[k]) for k in ("w2t_f32", "wfc_frag32") if k in obs]
+        sh = [bitwise(obs[k].reshape(-1), want[k]) for k in ("w2t_f32", "wfc_frag32") if k in obs]
     else:
         want = entry_shadows(P)
-        sh = [bitwise(obs[k], want[k]) for k in ("w2_bf16", "w2t_bf16", "wfc_frag") if k in obs]
+        sh = [bitwise(obs[k].reshape(-1), want[k]) for k in ("w2_bf16", "w2t_bf16", "wfc_frag") if k in obs]
         if plan["plain_fc_fresh"] and "wfc_bf16" in obs:
-            sh.append(bitwise(obs["wfc_bf16"], want["wfc_bf16"]))
+            sh.append(bitwise(obs["wfc_bf16"].reshape(-1), want["wfc_bf16"]))
     if sh:
         res["shadows"] = max(sh, key=lambda t: t[0])
 
@@ -499,17 +469,6 @@ def check_step(obs, before, x_u8, labels, B, plan):
         if mom and k in m_after:
             res[f"momentum_{k}"] = worst(m_after[k].reshape(SHAPES[k]), bref, bb + cb)
     return res
-
-
-def failing(res):
-    """The stages out of bound, in dependency order."""
-    return [s for s in ORDER if s in res and not res[s][0] <= 1.0]
-
-
-def report(res, chain, B, tag="STEP_RATIO"):
-    for s in ORDER:
-        if s in res:
-            print(f"{tag} {chain} {B} {s} {res[s][0]:.3e}")
 
 
 # ------------------------------------------------------------------------------- emulation

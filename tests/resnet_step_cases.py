@@ -86,17 +86,18 @@ sums of the slab, S_A, Q_A of its absolute values, m = S / P, v = max(Q / P - m^
 operators, bf16 roundings at the kernels' store points) and emits a trace in the recorder's
 format; ``plant=`` plants one wiring error (tests/test_resnet_step_bounds_cpu.py).
 """
+import functools
+
 import numpy as np
 import torch
 import torch.nn.functional as F
 
+import elementwise as EW
 import label_smoothing_cases as LS
 from ddp_amd.ops import kernel_bounds as K
 from ddp_amd.ops import reference as R
+from elementwise import BF, INF, U, bf, bits, bitwise, f64, n32, nchw, nhwc, worst  # noqa: F401  (reachable as S.worst ...)
 
-U = K.U
-BF = torch.bfloat16
-INF = float("inf")
 BN_EPS, BN_MOM = 1e-5, 0.1
 KERNELS = {"conv_gemm_fwd", "bn_finalize", "bn_apply", "maxpool_fwd", "avgpool_fwd", "sgemm", "xent", "bn_bwd",
            "conv_gemm_dgrad", "conv_gemm_wgrad", "grad_reduce", "maxpool_bwd", "avgpool_bwd", "sgd"}
@@ -106,23 +107,8 @@ STAGES = ("order", "weight_bf16", "pad4", "conv_y", "stats", "mean", "invstd", "
           "bn_apply", "maxpool", "avgpool", "head", "loss", "dlogits", "head_dx", "head_dw", "head_db", "avgpool_bwd",
           "bn_bwd_dres", "bn_dgamma", "bn_dbeta", "bn_bwd_dy", "dgrad", "wgrad_slab", "wgrad", "maxpool_bwd",
           "landing", "param", "momentum", "shadow_bf16", "shadow_pad4")
-
-
-def n32(v):
-    return float(np.float32(v))
-
-
-def f64(t):
-    return t.detach().cpu().double()
-
-
-def bf(t):
-    return t.detach().cpu().float().to(BF)
-
-
-def bits(t):
-    t = t.detach().cpu().contiguous()
-    return t.view({2: torch.int16, 4: torch.int32, 8: torch.int64, 1: torch.uint8}[t.element_size()])
+failing = functools.partial(EW.failing, order=STAGES)                       # failing(res)
+report = functools.partial(EW.report, order=STAGES, tag="RESNET_STEP_RATIO")  # report(res, case)
 
 
 # ------------------------------------------------------------------------------- topology
@@ -352,14 +338,6 @@ def produced_grads(st):
 
 
 # ------------------------------------------------------------------------------- references
-def nchw(t, dtype=torch.float64):
-    return t.detach().cpu().to(dtype).permute(0, 3, 1, 2).contiguous()
-
-
-def nhwc(t):
-    return t.permute(0, 2, 3, 1).contiguous()
-
-
 def conv_fwd(x, w, s, p, dtype=torch.float64):
     return nhwc(F.conv2d(nchw(x, dtype), nchw(w, dtype), stride=s, padding=p))
 
@@ -407,29 +385,6 @@ def bn_finalize_bounds(slab, count, eps, momentum, rm0=None, rv0=None):
         out["running_mean"] = (a * rm0 + mom * m, mom * dm + 3 * U * ((a * rm0).abs() + (mom * m).abs() + mom * dm))
         out["running_var"] = (a * rv0 + mom * f * v, mom * du + 3 * U * ((a * rv0).abs() + mom * (f * v + du)))
     return out
-
-
-def worst(out, ref, bound, exact_zero=None):
-    """(max |out - ref| / bound, index of the worst element); a non-finite output counts as
-    infinitely far out."""
-    o = f64(out)
-    if tuple(o.shape) != tuple(ref.shape):
-        return INF, ("shape", tuple(o.shape), tuple(ref.shape))
-    rr = (o - ref).abs() / (bound + 1e-300)
-    rr = torch.where(torch.isfinite(o), rr, torch.full_like(rr, INF))
-    if rr.numel() == 0:
-        return 0.0, ()
-    i = int(rr.reshape(-1).argmax())
-    return rr.reshape(-1)[i].item(), tuple(int(v) for v in np.unravel_index(i, tuple(rr.shape)))
-
-
-def bitwise(out, want):
-    """(0 or inf, first differing index): a stage that must match bit for bit."""
-    if out is None or want is None or tuple(out.shape) != tuple(want.shape) or out.dtype != want.dtype:
-        return INF, ("shape / dtype",)
-    a, b = bits(out).reshape(-1), bits(want).reshape(-1)
-    d = torch.nonzero(a != b)
-    return (0.0, ()) if d.numel() == 0 else (INF, (int(d[0]),))
 
 
 def _upd(res, stage, r, layer):
@@ -693,17 +648,6 @@ def check_step(trace, ctx, backwards=1, only=None, optimizer=True):
     if optimizer:
         check_optimizer(sgd, sts[-1], ctx, res, landing_only=only is not None)
     return res
-
-
-def failing(res):
-    """The stages out of bound, in dependency order."""
-    return [s for s in STAGES if s in res and not res[s][0] <= 1.0]
-
-
-def report(res, case, tag="RESNET_STEP_RATIO"):
-    for s in STAGES:
-        if s in res:
-            print(f"{tag} {case} {s} {res[s][0]:.3e}")
 
 
 # ------------------------------------------------------------------------------- emulation

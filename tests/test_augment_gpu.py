@@ -8,7 +8,6 @@ runs, odd: the 3-byte pixels' dword alignment and the rows' 16-byte alignment ch
 to row).  Every output is NaN-filled inside a larger allocation whose sentinel bands must
 stay untouched."""
 import json
-import math
 
 import pytest
 import torch
@@ -16,41 +15,25 @@ import torch
 import augment_cases as AC
 from ddp_amd.data import (IMAGENET_MEAN, IMAGENET_STD, AugPlan, Augment, DeviceImageLoader, DeviceImages, apply_fp32,
                           apply_reference)
+from elementwise import BF, Guarded
 
 pytestmark = pytest.mark.gpu
 dev = "cuda"
-BF = torch.bfloat16
-GUARD = 4096       # sentinel elements on each side
-SENTINEL = 1152.0  # exact in bf16
 SHAPES = [(12, 20), (7, 5)]
 N = 9
 
 
-class Guarded:
-    """A NaN-filled bf16 tensor between two sentinel bands; ``skew`` moves it by 4 elements, so
-    its base is 8- but not 16-byte aligned."""
-
-    def __init__(self, shape, skew=0):
-        n = math.prod(shape)
-        self.buf = torch.full((n + 2 * GUARD + 4,), SENTINEL, dtype=BF, device=dev)
-        self.lo = GUARD + 4 * skew
-        self.t = self.buf[self.lo:self.lo + n].view(shape)
-        self.t.fill_(float("nan"))
-
-    def check(self):
-        assert bool((self.buf[:self.lo] == SENTINEL).all()) and \
-            bool((self.buf[self.lo + self.t.numel():] == SENTINEL).all()), "write outside the output"
-        assert bool(torch.isfinite(self.t.float()).all()), "unwritten elements"
-        assert bool((self.t[..., 3] == 0).all()), "4th channel"
-        return self.t[..., :3].float().cpu()
-
-
 def gather(C, imgs, rows, affine, resample, idx, skew=0):
-    """The kernel on images ``imgs`` with the table ``rows`` (one per data-set image)."""
-    out = Guarded((len(idx), imgs.shape[1], imgs.shape[2], 4), skew)
+    """The kernel on images ``imgs`` with the table ``rows`` (one per data-set image), into a
+    NaN-filled output between two bands of 4096 sentinels; ``skew`` moves it by 4 elements, so its
+    base is 8- but not 16-byte aligned."""
+    out = Guarded((len(idx), imgs.shape[1], imgs.shape[2], 4), BF, guard=4096, skew=skew)
     C.image_gather_aug_nhwc4(imgs.to(dev), torch.as_tensor(idx).to(dev), rows.to(dev), affine, out.t, resample)
     torch.cuda.synchronize()
-    return out.check()
+    out.check("the output")
+    assert bool(torch.isfinite(out.t.float()).all()), "unwritten elements"
+    assert bool((out.t[..., 3] == 0).all()), "4th channel"
+    return out.t[..., :3].float().cpu()
 
 
 def batches(n):

@@ -20,99 +20,18 @@ non-finite (infinitely out of bound), and on a ragged batch the rows past B must
 Run with -s for the STEP_RATIO <chain> <B> <stage> <error / bound> lines;
 profiles/engine_step/README.md records them.
 """
+import functools
+
 import pytest
 import torch
 
-import engine_step_cases as E
+import engine_step_harness as H
+from engine_step_harness import begin
 
 pytestmark = pytest.mark.gpu
-dev = "cuda"
-NAMES = {"w1": "net.0.weight", "b1": "net.0.bias", "w2": "net.2.weight", "b2": "net.2.bias", "wfc": "fl.weight",
-         "bfc": "fl.bias"}
-POISON = ("a1", "a2", "dz1", "dz2", "fc_part", "dlogits", "loss_rows", "w2slab", "w1slab")
-SHADOWS = ("w2_bf16", "w2t_bf16", "wfc_frag", "wfc_bf16")
-LR = 0.01
-
-
-def _setup(n=256, B=32, fuse_level=0, momentum=0.0, weight_decay=0.0, fuse_opt=True, use_graph=False, graph_steps=5, **eo):
-    from ddp_amd.data import DeviceMNIST, synthetic_mnist
-    from ddp_amd.engine import EngineOptions, FusedSimpleCNNEngine
-    from ddp_amd.models import SimpleCNN
-    from ddp_amd.ops import FusedSGD
-
-    torch.manual_seed(0)
-    model = SimpleCNN().to(dev)
-    opt = FusedSGD(model, lr=LR, momentum=momentum, weight_decay=weight_decay)
-    imgs, labels = synthetic_mnist(n)
-    eng = FusedSimpleCNNEngine(model, opt, DeviceMNIST(imgs, labels, dev), B, 1, 0,
-                               opts=EngineOptions(graph_steps=graph_steps, use_graph=use_graph, fuse_level=fuse_level,
-                                                  fuse_opt=fuse_opt, store_a1=1, **eo))
-    eng.refresh()
-    return eng, imgs, labels
-
-
-def begin(eng, epoch=0):
-    eng.sync_from_torch()
-    eng.start_epoch(epoch)
-
-
-def by_name(eng, flat):
-    return {k: eng.fs.view(flat, v).detach().cpu().clone() for k, v in NAMES.items()}
-
-
-def checked_step(eng, imgs, labels, B, chain, first_step=False):
-    """Snapshot, poison, one eager step of B images, check_step on what the chain materialises."""
-    t, level, mom = eng.t, int(eng.cfg["fuse_level"]), eng.cfg["momentum"] != 0.0
-    eng.synchronize()
-    torch.cuda.synchronize()
-    k = int(t["step_ctr"].item())
-    before = by_name(eng, eng.fs.params)
-    obs = {s: t[s].cpu().clone() for s in SHADOWS}
-    obs["loss_hist_before"] = t["loss_hist"].cpu().clone()
-    if mom and not first_step:
-        obs["momentum_before"] = by_name(eng, t["momentum"])
-    idx = eng.sampler.indices()[k * eng.B:k * eng.B + B]
-    assert idx.numel() == B
-    for s in POISON:
-        t[s].fill_(float("nan"))
-    for v in NAMES.values():  # (the views, not the alignment gaps the flat SGD kernel also sweeps)
-        eng.fs.view(eng.fs.grads, v).fill_(float("nan"))
-    torch.cuda.synchronize()
-    eng.eng.step(B, eng.B)
-    eng.synchronize()
-    torch.cuda.synchronize()
-    assert eng.eng.sync_error == 0
-    assert int(t["step_ctr"].item()) == k + 1
-    l3 = bool(eng.eng.last_level3)
-    assert l3 == (level >= 3)
-    stored = ["a1", "a2", "dz2", "w2slab", "w1slab", "loss_hist"]
-    stored += ["dz1"] if level == 0 else []
-    stored += ["fc_part"] if not l3 else []                  # level 3 hands the partials over as granules
-    stored += ["dlogits", "loss_rows"] if (level == 0 or l3) else []  # level 1: fc_bwd's prologue keeps them in LDS
-    obs.update({s: t[s].cpu().clone() for s in stored})
-    grads = by_name(eng, eng.fs.grads)
-    if eng.cfg["fuse_opt"]:  # the fused optimizer consumes the fc weight gradient in registers
-        assert bool(torch.isnan(grads.pop("wfc")).all())
-    obs["grads"] = grads
-    obs["params_after"] = by_name(eng, eng.fs.params)
-    if mom:
-        obs["momentum_after"] = by_name(eng, t["momentum"])
-    g = eng.opt.param_groups[0]
-    plan = E.make_plan(B, level=level, pxt_fwd=eng.opts.pxt_fwd, pxt_dgrad=eng.opts.pxt_dgrad, wgrad_rows=eng.wgrad_rows,
-                       max_batch=eng.B, k=k, lr=g["lr"], momentum=g["momentum"], dampening=g["dampening"],
-                       weight_decay=g["weight_decay"], nesterov=g["nesterov"], first_step=first_step)
-    res = E.check_step(obs, before, imgs[idx], labels[idx], B, plan)
-    E.report(res, chain, B)
-    bad = E.failing(res)
-    assert not bad, f"{chain} B={B} step {k}: out of bound at {[(s, res[s]) for s in bad]}"
-    want = {"shadows", "a2", "dz2", "loss_hist", "w2slab", "w1slab", "grad_w1", "grad_b1", "grad_w2", "grad_b2", "grad_bfc"}
-    want |= {f"param_{p}" for p in E.PARAMS} | {s for s in stored if s not in ("loss_hist",)}
-    assert want <= set(res), sorted(want - set(res))
-    if B < eng.B:  # a ragged batch leaves the rows past B alone
-        per = {"a1": E.HW * E.C1, "dz1": E.HW * E.C1, "a2": E.HW * E.C2, "dz2": E.HW * E.C2, "dlogits": E.NO, "loss_rows": 1}
-        for s, n in per.items():
-            assert bool(torch.isnan(t[s].reshape(-1)[B * n:].float()).all()), f"{chain}: {s} written past row {B}"
-    return res
+# the bf16 description: a1 stored for the mask (store_a1 = 1), the level-0 chain unless a test says otherwise
+_setup = functools.partial(H.setup, H.BF16)
+checked_step = functools.partial(H.checked_step, H.BF16)
 
 
 # ------------------------------------------------------------------------------- level 0

@@ -20,106 +20,20 @@ tests/test_fp32_gpu.py already launches.
 Run with -s for the STEP_RATIO fp32_<chain> <B> <stage> <error / bound> lines;
 profiles/engine_step/README.md records them.
 """
+import functools
+
 import pytest
 import torch
 
-import engine_step_cases as E
+import engine_step_harness as H
+from engine_step_harness import begin
 
 pytestmark = pytest.mark.gpu
-dev = "cuda"
-NAMES = {"w1": "net.0.weight", "b1": "net.0.bias", "w2": "net.2.weight", "b2": "net.2.bias", "wfc": "fl.weight",
-         "bfc": "fl.bias"}
-POISON = ("a2", "dz2", "fc_part", "dlogits", "loss_rows", "w2slab", "w1slab")
-SHADOWS = ("w2t_f32", "wfc_frag32")
-LR = 0.01
 L1 = dict(fuse_level=1, wgrad_split=1)  # the round-3 kernels: one conv backward block per row / chunk
 L3 = dict(fuse_level=3, wgrad_split=2, momentum=0.9, weight_decay=1e-4)
-
-
-def _setup(n=256, B=32, momentum=0.0, weight_decay=0.0, use_graph=False, graph_steps=5, **eo):
-    from ddp_amd.data import DeviceMNIST, synthetic_mnist
-    from ddp_amd.engine import EngineOptions, FusedSimpleCNNEngine
-    from ddp_amd.models import SimpleCNN
-    from ddp_amd.ops import FusedSGD
-
-    torch.manual_seed(0)
-    model = SimpleCNN(compute_dtype=torch.float32).to(dev)
-    opt = FusedSGD(model, lr=LR, momentum=momentum, weight_decay=weight_decay)
-    imgs, labels = synthetic_mnist(n)
-    eng = FusedSimpleCNNEngine(model, opt, DeviceMNIST(imgs, labels, dev), B, 1, 0,
-                               opts=EngineOptions(graph_steps=graph_steps, use_graph=use_graph, dtype="fp32", **eo))
-    eng.refresh()
-    assert eng.dtype == "fp32" and eng.store_a1 == 0 and eng.opts.pxt_fwd == 2 and "a1" not in eng.t
-    return eng, imgs, labels
-
-
-def begin(eng, epoch=0):
-    eng.sync_from_torch()
-    eng.start_epoch(epoch)
-
-
-def by_name(eng, flat):
-    return {k: eng.fs.view(flat, v).detach().cpu().clone() for k, v in NAMES.items()}
-
-
-def checked_step(eng, imgs, labels, B, chain, first_step=False):
-    """Snapshot, poison, one eager step of B images, check_step on what the chain materialises."""
-    from ddp_amd.ops.functional import wgrad_rows
-
-    t, level, mom = eng.t, int(eng.cfg["fuse_level"]), eng.cfg["momentum"] != 0.0
-    eng.synchronize()
-    torch.cuda.synchronize()
-    k = int(t["step_ctr"].item())
-    before = by_name(eng, eng.fs.params)
-    obs = {s: t[s].cpu().clone() for s in SHADOWS}
-    obs["loss_hist_before"] = t["loss_hist"].cpu().clone()
-    if mom and not first_step:
-        obs["momentum_before"] = by_name(eng, t["momentum"])
-    idx = eng.sampler.indices()[k * eng.B:k * eng.B + B]
-    assert idx.numel() == B
-    for s in POISON:
-        t[s].fill_(float("nan"))
-    for v in NAMES.values():  # (the views, not the alignment gaps the flat SGD kernel also sweeps)
-        eng.fs.view(eng.fs.grads, v).fill_(float("nan"))
-    torch.cuda.synchronize()
-    eng.eng.step(B, eng.B)
-    eng.synchronize()
-    torch.cuda.synchronize()
-    assert eng.eng.sync_error == 0
-    assert int(t["step_ctr"].item()) == k + 1
-    l3 = bool(eng.eng.last_level3)
-    assert l3 == (level >= 3)
-    stored = ["a2", "dz2", "w2slab", "w1slab", "loss_hist"]
-    stored += ["dlogits", "loss_rows"] if l3 else ["fc_part"]  # level 3: granules; level 1: dL stays in LDS
-    obs.update({s: t[s].cpu().clone() for s in stored})
-    grads = by_name(eng, eng.fs.grads)
-    if eng.cfg["fuse_opt"]:  # the fused optimizer consumes the fc weight gradient in registers
-        assert bool(torch.isnan(grads.pop("wfc")).all())
-    obs["grads"] = grads
-    obs["params_after"] = by_name(eng, eng.fs.params)
-    if mom:
-        obs["momentum_after"] = by_name(eng, t["momentum"])
-    g = eng.opt.param_groups[0]
-    assert eng.wgrad_rows == wgrad_rows(28, eng.B, torch.float32)
-    plan = E.make_plan(B, level=level, pxt_fwd=eng.opts.pxt_fwd, pxt_dgrad=eng.opts.pxt_dgrad, wgrad_rows=eng.wgrad_rows,
-                       max_batch=eng.B, k=k, lr=g["lr"], momentum=g["momentum"], dampening=g["dampening"],
-                       weight_decay=g["weight_decay"], nesterov=g["nesterov"], first_step=first_step, prec="fp32")
-    # the row counts the reference derives are the launchers'
-    nRC = -(-28 // eng.wgrad_rows)
-    assert eng.C.conv3x3_wgrad_blocks(B, 28, eng.wgrad_rows) == B * nRC
-    assert eng.C.conv3x3_dgrad_blocks(B, 28, 28, eng.opts.pxt_dgrad) == -(-B * E.HW // plan["CH1"])
-    res = E.check_step(obs, before, imgs[idx], labels[idx], B, plan)
-    E.report(res, f"fp32_{chain}", B)
-    bad = E.failing(res)
-    assert not bad, f"fp32 {chain} B={B} step {k}: out of bound at {[(s, res[s]) for s in bad]}"
-    want = E.fp32_stages(level, mom) - ({"grad_wfc"} if eng.cfg["fuse_opt"] else set())
-    assert set(res) == want, sorted(want ^ set(res))
-    if B < eng.B:  # a ragged batch leaves the rows past B alone
-        per = {"a2": E.HW * E.C2, "dz2": E.HW * E.C2}
-        per.update({"dlogits": E.NO, "loss_rows": 1} if l3 else {})
-        for s, n in per.items():
-            assert bool(torch.isnan(t[s].reshape(-1)[B * n:]).all()), f"fp32 {chain}: {s} written past row {B}"
-    return res
+# the fp32 description: dtype="fp32" fixed, the chain left to the engine's defaults unless a test names it
+_setup = functools.partial(H.setup, H.FP32)
+checked_step = functools.partial(H.checked_step, H.FP32)
 
 
 # ------------------------------------------------------------------------------- level 1

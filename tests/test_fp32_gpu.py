@@ -5,9 +5,12 @@ module-path SimpleCNN against the stock fp32 model (the reference's nn.Conv2d / 
 /root/reference/model.py:8-16) at <= 1e-4, and the fp32 fused engine's step against the
 float64 oracle ``simple_cnn_step_exact``.  (The engine step per element and stage, with
 a-priori bounds instead of norms: tests/test_engine_step_fp32_elementwise_gpu.py.)"""
+import functools
+
 import pytest
 import torch
 
+import elementwise
 from ddp_amd.ops import reference as R
 
 pytestmark = pytest.mark.gpu
@@ -15,12 +18,7 @@ dev = "cuda"
 F64 = torch.float64
 
 
-def rnd(*shape, scale=1.0, seed=0, relu=False):
-    g = torch.Generator().manual_seed(seed)
-    t = torch.randn(*shape, generator=g) * scale
-    if relu:
-        t = torch.relu(t)
-    return t.to(dev)
+rnd = functools.partial(elementwise.rnd, dtype=torch.float32)  # fp32 operands
 
 
 def d(t):

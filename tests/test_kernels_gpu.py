@@ -10,17 +10,10 @@ import torch
 
 from ddp_amd.ops import reference as R
 
+from elementwise import BF, rnd
+
 pytestmark = pytest.mark.gpu
 dev = "cuda"
-BF = torch.bfloat16
-
-
-def rnd(*shape, scale=1.0, seed=0, relu=False):
-    g = torch.Generator().manual_seed(seed)
-    t = torch.randn(*shape, generator=g) * scale
-    if relu:
-        t = torch.relu(t)
-    return t.to(BF).to(dev)
 
 
 def close(a, b, rtol=2e-2, atol=2e-2):

@@ -5,37 +5,15 @@ reference within the a-priori bounds that tests/test_label_smoothing_cpu.py deri
 ``CrossEntropyLoss(label_smoothing=)``: SimpleCNN's module path against the CPU model, and
 ResNet-18's captured step graph against its eager step.  Outputs are NaN-prefilled and
 guarded as in tests/test_resnet_ops_elementwise_gpu.py.  Run with -s for the LS_RATIO lines."""
-import math
-
 import pytest
 import torch
 
 import label_smoothing_cases as LS
 from ddp_amd.ops import reference as R
+from elementwise import F32, Guarded, bits
 
 pytestmark = pytest.mark.gpu
 dev = "cuda"
-F32 = torch.float32
-GUARD = 8192
-SENTINEL = 1152.0
-
-
-class Guarded:
-    """A NaN-filled float32 tensor between two sentinel bands of one allocation."""
-
-    def __init__(self, shape):
-        n = math.prod(shape)
-        self.buf = torch.full((n + 2 * GUARD,), SENTINEL, dtype=F32, device=dev)
-        self.t = self.buf[GUARD:GUARD + n].view(shape)
-        self.t.fill_(float("nan"))
-
-    def check(self, what):
-        assert bool((self.buf[:GUARD] == SENTINEL).all()) and bool((self.buf[-GUARD:] == SENTINEL).all()), \
-            f"write outside {what}"
-
-
-def bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32)
 
 
 def held(name, shape, out, ref, bound, what):
@@ -48,9 +26,9 @@ def run(C, lg, lab, eps, what, G=1, part=None, bias=None, want_extras=False, dbi
     """One launch through the binding on guarded outputs; returns (dlogits, loss, logits_out, dbias)."""
     B, NC = lg.shape
     g = LS.f32(1.0 / B)
-    dl, loss = Guarded((B, NC)), Guarded((1,))
-    lo = Guarded((B, NC)) if want_extras else None
-    db = Guarded((NC,)) if want_extras else None
+    dl, loss = Guarded((B, NC), F32), Guarded((1,), F32)
+    lo = Guarded((B, NC), F32) if want_extras else None
+    db = Guarded((NC,), F32) if want_extras else None
     kw = {} if eps is None else {"label_smoothing": eps}
     C.xent(lg if part is None else part, G, bias, lab, lo.t if lo else None, dl.t, loss.t, db.t if db else None, g,
            dbias_scale, **kw)

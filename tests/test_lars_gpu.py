@@ -15,6 +15,7 @@ import torch
 from ddp_amd.ops import FusedLARS, FusedSGD, LRSchedule
 from ddp_amd.ops import kernel_bounds as kb
 from ddp_amd.ops.lars import lars_layout
+from elementwise import Guarded, bits
 from test_lars_cpu import (ADAPTS, BEGINS, COEF, EPS, LENS, LR, MOM, N, SEGS, TC, WDS, ZERO_G, ZERO_W, check_bounds,
                            make_inputs)
 
@@ -29,16 +30,12 @@ NITEMS = sum(kb.lars_items(m) for m in LENS)
 
 
 def guarded(n, dtype, fill=SENT):
-    buf = torch.full((n + 2 * G,), fill, dtype=dtype, device=dev)
-    return buf, buf[G:G + n]
+    g = Guarded(n, dtype, fill, dev, guard=G, sentinel=fill)  # (the view starts as sentinel too)
+    return g.buf, g.t
 
 
 def guards_intact(buf, n, fill=SENT):
     return bool((buf[:G] == fill).all()) and bool((buf[G + n:] == fill).all())
-
-
-def bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32)
 
 
 def with_nan_padding(x):

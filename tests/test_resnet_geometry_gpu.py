@@ -21,52 +21,19 @@ Every output, the split-K workspace and every slab is carved out of a larger buf
 sentinel bands on both sides (nothing outside is written) and pre-filled with NaN (every
 element is written); masked data-gradient elements are exactly 0.
 """
-import math
-
 import pytest
 import torch
 import torch.nn.functional as F
 
+from elementwise import BF, Guarded, U, f64, nchw, nhwc, report_ratio, rnd
+
 pytestmark = pytest.mark.gpu
 dev = "cuda"
-BF = torch.bfloat16
-U = 2.0 ** -24
-GUARD = 8192       # sentinel elements on each side (a multiple of 8: 16-byte alignment kept)
-SENTINEL = 1152.0  # 9 * 128: exact in bf16 and fp32
-
-
-def rnd(*shape, scale=1.0, seed=0, relu=False):
-    g = torch.Generator().manual_seed(seed)
-    t = torch.randn(*shape, generator=g) * scale
-    return (torch.relu(t) if relu else t).to(BF).to(dev)
-
-
-class Guarded:
-    """A NaN-filled tensor between two sentinel bands of one allocation."""
-
-    def __init__(self, shape, dtype, fill=float("nan")):
-        n = math.prod(shape)
-        self.buf = torch.full((n + 2 * GUARD,), SENTINEL, dtype=dtype, device=dev)
-        self.t = self.buf[GUARD:GUARD + n].view(shape)
-        self.t.fill_(fill)
-        assert self.t.is_contiguous() and self.t.data_ptr() % 16 == 0
-
-    def check(self, what=""):
-        lo, hi = self.buf[:GUARD], self.buf[-GUARD:]
-        assert bool((lo == SENTINEL).all()) and bool((hi == SENTINEL).all()), f"write outside {what}"
-
-
-def nchw(t):  # NHWC device tensor -> float64 NCHW on the CPU
-    return t.detach().cpu().double().permute(0, 3, 1, 2).contiguous()
-
-
-def nhwc(t):
-    return t.permute(0, 2, 3, 1).contiguous()
 
 
 def ratio_bf16(out, ref, A, n, what):
     """max |out - ref| / bound of a bf16 output; asserts every element written and in bound."""
-    o = out.detach().cpu().double()
+    o = f64(out)
     assert bool(torch.isfinite(o).all()), f"{what}: unwritten / non-finite elements"
     bound = 2.0 ** -8 * ref.abs() + 2 * n * U * A + 1e-30
     r = ((o - ref).abs() / bound).max().item()
@@ -75,7 +42,7 @@ def ratio_bf16(out, ref, A, n, what):
 
 
 def ratio_f32(out, ref, A, n, what):
-    o = out.detach().cpu().double()
+    o = f64(out)
     assert bool(torch.isfinite(o).all()), f"{what}: unwritten / non-finite elements"
     bound = 2 * n * U * A + 1e-30
     r = ((o - ref).abs() / bound).max().item()
@@ -85,10 +52,10 @@ def ratio_f32(out, ref, A, n, what):
 
 def ratio_stats(stats, y, what):
     """Stats slab [rows][2][C] summed over rows (fp64) vs the stored bf16 y."""
-    s = stats.detach().cpu().double()
+    s = f64(stats)
     assert bool(torch.isfinite(s).all()), f"{what}: unwritten stats rows"
     s = s.sum(0)
-    yd = y.detach().cpu().double().reshape(-1, y.shape[-1])
+    yd = f64(y).reshape(-1, y.shape[-1])
     P = yd.shape[0]
     b0 = 2 * P * U * yd.abs().sum(0) + 1e-30
     b1 = 2 * P * U * (yd * yd).sum(0) + 1e-30
@@ -98,7 +65,7 @@ def ratio_stats(stats, y, what):
 
 
 def report(family, shape, r):
-    print(f"GEOM_RATIO {family} {shape} {r:.4f}")
+    report_ratio(r, family, shape, tag="GEOM_RATIO")
 
 
 class Conv:
@@ -118,7 +85,7 @@ class Conv:
         self.dx_abs = nhwc(torch.nn.grad.conv2d_input(xd.shape, wd.abs(), dyd.abs(), **kw))
         self.dw_ref = nhwc(torch.nn.grad.conv2d_weight(xd, wd.shape, dyd, **kw)).reshape(-1)
         self.dw_abs = nhwc(torch.nn.grad.conv2d_weight(xd.abs(), wd.shape, dyd.abs(), **kw)).reshape(-1)
-        self.xpos = self.x.detach().cpu().double() > 0
+        self.xpos = f64(self.x) > 0
         self.P = N * self.OH * self.OW
         self.row = Cout * K * K * Cin
 
@@ -169,7 +136,7 @@ def run_dgrad(C, cv, bp, bc, splits, parity, halo, mask, want_halo=None):
     ref, A = cv.dx_ref, cv.dx_abs
     if mask:
         ref = torch.where(cv.xpos, ref, torch.zeros_like(ref))
-        got = dx.t.detach().cpu().double()
+        got = f64(dx.t)
         assert bool((got[~cv.xpos] == 0).all()), f"{what}: masked elements must be exactly 0"
     r = ratio_bf16(dx.t, ref, A, K * K * Cout, what)
     for g_ in (dx, part):
@@ -203,7 +170,7 @@ def run_wgrad(C, cv, ppc, accum=False, ks=0):
         slab.check(what)
     dw.check(what)
     if accum:  # the prior is one more term of the sum
-        pd = prior.cpu().double()
+        pd = f64(prior)
         return ratio_f32(dw.t, pd + cv.dw_ref, cv.dw_abs + pd.abs(), cv.P + 1, what)
     return ratio_f32(dw.t, cv.dw_ref, cv.dw_abs, cv.P, what)
 

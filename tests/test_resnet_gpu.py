@@ -3,15 +3,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from elementwise import BF, rnd
+
 pytestmark = pytest.mark.gpu
 dev = "cuda"
-BF = torch.bfloat16
-
-
-def rnd(*shape, scale=1.0, seed=0, relu=False):
-    g = torch.Generator().manual_seed(seed)
-    t = torch.randn(*shape, generator=g) * scale
-    return (torch.relu(t) if relu else t).to(BF).to(dev)
 
 
 def relerr(a, b):

@@ -30,45 +30,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from elementwise import BF, Guarded, U, f64, nchw, nhwc, rnd
+
 pytestmark = pytest.mark.gpu
 dev = "cuda"
-BF = torch.bfloat16
-U = 2.0 ** -24
-GUARD = 8192       # sentinel elements on each side (a multiple of 8: 16-byte alignment kept)
-SENTINEL = 1152.0  # 9 * 128: exact in bf16 and fp32
-
-
-def rnd(*shape, scale=1.0, seed=0, relu=False):
-    g = torch.Generator().manual_seed(seed)
-    t = torch.randn(*shape, generator=g) * scale
-    return (torch.relu(t) if relu else t).to(BF).to(dev)
-
-
-class Guarded:
-    """A tensor between two sentinel bands of one allocation: NaN-filled (outputs, workspaces)
-    or holding `value` (a residual, which the kernel must only read)."""
-
-    def __init__(self, shape, dtype, value=None):
-        n = math.prod(shape)
-        self.buf = torch.full((n + 2 * GUARD,), SENTINEL, dtype=dtype, device=dev)
-        self.t = self.buf[GUARD:GUARD + n].view(shape)
-        if value is None:
-            self.t.fill_(float("nan"))
-        else:
-            self.t.copy_(value)
-        assert self.t.is_contiguous() and self.t.data_ptr() % 16 == 0
-
-    def check(self, what=""):
-        lo, hi = self.buf[:GUARD], self.buf[-GUARD:]
-        assert bool((lo == SENTINEL).all()) and bool((hi == SENTINEL).all()), f"write outside {what}"
-
-
-def nchw(t):  # NHWC device tensor -> float64 NCHW on the CPU
-    return t.detach().cpu().double().permute(0, 3, 1, 2).contiguous()
-
-
-def nhwc(t):
-    return t.permute(0, 2, 3, 1).contiguous()
 
 
 def affine(Cout, seed):
@@ -131,7 +96,7 @@ def run(C, cv, family, res, relu, bp=0, bc=0, splits=0, halo=-1, want_halo=None,
     ref = torch.relu(pre) if relu else pre
     bound = (2.0 ** -8 * ref.abs() + (cv.K + 2) * U * sc.abs() * cv.A
              + 3 * U * ((cv.acc * sc).abs() + sh.abs() + rd.abs()) + 1e-30)
-    o = y.t.detach().cpu().double()
+    o = f64(y.t)
     assert bool(torch.isfinite(o).all()), f"{what}: unwritten / non-finite elements"
     rr = (o - ref).abs() / bound
     r = rr.max().item()

@@ -67,52 +67,15 @@ sides (nothing outside is written) and pre-filled with NaN (every element is wri
 Run with -s for the OPS_RATIO <family> <shape> <error / bound> lines;
 profiles/resnet_ops/README.md records the largest per family and shape.
 """
-import math
-
 import pytest
 import torch
 
 from ddp_amd.ops import reference as R
+from elementwise import BF, F32, Guarded, U, bits, f64, report_ratio, rnd
 
 pytestmark = pytest.mark.gpu
 dev = "cuda"
-BF = torch.bfloat16
-F32 = torch.float32
-U = 2.0 ** -24
-GUARD = 8192       # sentinel elements on each side (a multiple of 8: 16-byte alignment kept)
-SENTINEL = 1152.0  # 9 * 128: exact in bf16 and fp32
-SENTINEL_U8 = 165
 BN_BWD_PX_DEFAULT = 392  # resnet_ops.hip g_bn_bwd_px
-
-
-def rnd(*shape, scale=1.0, seed=0, relu=False, dtype=BF):
-    g = torch.Generator().manual_seed(seed)
-    t = torch.randn(*shape, generator=g) * scale
-    return (torch.relu(t) if relu else t).to(dtype).to(dev)
-
-
-class Guarded:
-    """A NaN-filled (uint8: 255-filled) tensor between two sentinel bands of one allocation."""
-
-    def __init__(self, shape, dtype):
-        n = math.prod(shape)
-        self.sent = SENTINEL_U8 if dtype == torch.uint8 else SENTINEL
-        self.buf = torch.full((n + 2 * GUARD,), self.sent, dtype=dtype, device=dev)
-        self.t = self.buf[GUARD:GUARD + n].view(shape)
-        self.t.fill_(255 if dtype == torch.uint8 else float("nan"))
-        assert self.t.is_contiguous() and self.t.data_ptr() % 16 == 0
-
-    def check(self, what=""):
-        lo, hi = self.buf[:GUARD], self.buf[-GUARD:]
-        assert bool((lo == self.sent).all()) and bool((hi == self.sent).all()), f"write outside {what}"
-
-
-def f64(t):
-    return t.detach().cpu().double()
-
-
-def bits(t):
-    return t.detach().cpu().contiguous().view(torch.int16 if t.dtype == BF else torch.int32)
 
 
 def ratio(family, shape, out, ref, bound, what):
@@ -122,7 +85,7 @@ def ratio(family, shape, out, ref, bound, what):
     assert bool(torch.isfinite(o).all()), f"{what}: unwritten / non-finite elements"
     rr = (o - ref).abs() / (bound + 1e-30)
     r = rr.max().item()
-    print(f"OPS_RATIO {family} {shape} {r:.4f}")
+    report_ratio(r, family, shape, tag="OPS_RATIO")
     if r > 1.0:
         i = tuple(int(v) for v in torch.nonzero(rr == rr.max())[0])
         what += f" at {i}: out {o[i].item()!r} ref {ref[i].item()!r}; {int((rr > 1).sum())} elements out of bound"

@@ -12,7 +12,7 @@ D = torch.float64
 TOL = 1e-12
 
 
-def rnd(*shape, seed=0):
+def randn64(*shape, seed=0):
     return torch.randn(*shape, generator=torch.Generator().manual_seed(seed), dtype=D)
 
 
@@ -32,10 +32,10 @@ def nhwc(t):
 @pytest.mark.parametrize("N,H,W,C", [(3, 5, 7, 16), (2, 9, 3, 24)])
 @pytest.mark.parametrize("res,relu", [(False, False), (True, False), (False, True), (True, True)])
 def test_batchnorm_matches_torch_double(N, H, W, C, res, relu):
-    x = rnd(N, H, W, C, seed=1) * 1.5 + 0.3
-    r = rnd(N, H, W, C, seed=2) if res else None
-    gamma, beta = rnd(C, seed=3).abs() + 0.5, rnd(C, seed=4) * 0.3
-    dout = rnd(N, H, W, C, seed=5)
+    x = randn64(N, H, W, C, seed=1) * 1.5 + 0.3
+    r = randn64(N, H, W, C, seed=2) if res else None
+    gamma, beta = randn64(C, seed=3).abs() + 0.5, randn64(C, seed=4) * 0.3
+    dout = randn64(N, H, W, C, seed=5)
     bn = torch.nn.BatchNorm2d(C, dtype=D).train()
     with torch.no_grad():
         bn.weight.copy_(gamma)
@@ -80,7 +80,7 @@ def torch_pool(x):
 @pytest.mark.parametrize("N,H,W,C", [(2, 7, 5, 8), (1, 9, 9, 16), (2, 1, 1, 8), (2, 2, 4, 8)])
 @pytest.mark.parametrize("kind", ["randn", "relu", "quantised"])
 def test_maxpool_matches_torch_double(N, H, W, C, kind):
-    x = rnd(N, H, W, C, seed=7)
+    x = randn64(N, H, W, C, seed=7)
     if kind == "relu":
         x = torch.relu(x)  # zeros: ties everywhere
     elif kind == "quantised":
@@ -94,7 +94,7 @@ def test_maxpool_matches_torch_double(N, H, W, C, kind):
         # the tie rule decided something: an earlier tap holds the same value as a later one
         win = F.unfold(F.pad(nchw(x), (1, 1, 1, 1), value=float("-inf")), 3, stride=2).view(N, C, 9, -1)
         assert ((win == win.max(2, keepdim=True).values).sum(2) > 1).any()
-    dy = rnd(*y.shape, seed=8)
+    dy = randn64(*y.shape, seed=8)
     ty.backward(nchw(dy))
     close(bwd(dy), nhwc(xr.grad))
     # float32 routing: at most 4 terms per input pixel, the same values up to fp32 rounding
@@ -115,18 +115,18 @@ def test_maxpool_tie_rule_on_constant_input():
 
 @pytest.mark.parametrize("N,H,W,C", [(3, 3, 3, 64), (2, 7, 5, 24)])
 def test_avgpool_matches_torch_double(N, H, W, C):
-    x = rnd(N, H, W, C, seed=9)
+    x = randn64(N, H, W, C, seed=9)
     xr = nchw(x).requires_grad_(True)
     ref = F.adaptive_avg_pool2d(xr, 1).flatten(1)
     close(R.avgpool64(x), ref.detach())
-    dy = rnd(N, C, seed=10)
+    dy = randn64(N, C, seed=10)
     ref.backward(dy)
     close(R.avgpool_bwd64(dy, H, W), nhwc(xr.grad))
 
 
 @pytest.mark.parametrize("B,C", [(5, 65), (7, 127)])
 def test_xent_matches_torch_double(B, C):
-    x = rnd(B, C, seed=11) * 3
+    x = randn64(B, C, seed=11) * 3
     x[1] = 2.5          # all logits equal
     x[2] += 1e4         # large offset
     x[3] *= 6           # wide spread
@@ -147,7 +147,7 @@ def test_xent_matches_torch_double(B, C):
 
 @pytest.mark.parametrize("M,N,K", [(5, 33, 65), (17, 10, 7)])
 def test_gemm_matches_torch_double(M, N, K):
-    A, Bm, bias, prior = rnd(M, K, seed=12), rnd(K, N, seed=13), rnd(N, seed=14), rnd(M, N, seed=15)
+    A, Bm, bias, prior = randn64(M, K, seed=12), randn64(K, N, seed=13), randn64(N, seed=14), randn64(M, N, seed=15)
     close(R.gemm64(A, Bm), A @ Bm)
     close(R.gemm64(A, Bm, bias, 0.37, prior), 0.37 * (A @ Bm) + bias + prior)
     # low-precision operands are widened, never rounded

@@ -42,10 +42,10 @@ import pytest
 import torch
 
 import resnet_step_cases as S
+from elementwise import BF, Guarded
 
 pytestmark = pytest.mark.gpu
 dev = "cuda"
-BF = torch.bfloat16
 _RESULTS = {}
 
 
@@ -234,15 +234,6 @@ def test_cases_reach_both_weight_gradient_paths_and_every_accumulate_flag(C):
 
 
 # ------------------------------------------------------------------- bn_finalize per element
-GUARD, SENT = 1024, 1152.0
-
-
-def guarded(n):
-    buf = torch.full((n + 2 * GUARD,), SENT, device=dev)
-    buf[GUARD:GUARD + n] = float("nan")
-    return buf, buf[GUARD:GUARD + n]
-
-
 # (rows, C, count)
 FIN_CASES = [(1, 64, 1), (1, 512, 16), (1, 96, 50), (7, 96, 896), (130, 64, 1040), (200, 512, 1600), (65, 96, 65)]
 
@@ -265,8 +256,8 @@ def test_bn_finalize_per_element(C, rows, Cc, count):
     slab = torch.stack([x.sum(1), (x * x).sum(1)], 1).float().to(dev)  # [rows][2][C]
     rm0 = torch.randn(Cc, generator=g).to(dev)
     rv0 = (torch.rand(Cc, generator=g) + 0.5).to(dev)
-    bufs = [guarded(Cc) for _ in range(4)]
-    (_, rm), (_, rv), (_, mean), (_, invstd) = bufs
+    bufs = [Guarded(Cc, torch.float32, guard=1024) for _ in range(4)]
+    rm, rv, mean, invstd = (b.t for b in bufs)
     rm.copy_(rm0)
     rv.copy_(rv0)
     nbt = torch.tensor(5, device=dev)
@@ -279,8 +270,8 @@ def test_bn_finalize_per_element(C, rows, Cc, count):
         print(f"RESNET_STEP_RATIO bn_finalize_{(rows, Cc, count)} {k} {r:.3e}")
         assert r <= 1.0, f"bn_finalize {(rows, Cc, count)} {k}: error / bound = {r:.3f} at channel {i}"
     assert int(nbt) == 6
-    for buf, _ in bufs:
-        assert bool((buf[:GUARD] == SENT).all()) and bool((buf[-GUARD:] == SENT).all()), "write outside C channels"
+    for b_ in bufs:
+        b_.check("C channels")
     # the bound itself says where fp32 runs out: the cancelling channel is allowed parts per thousand or more
     ref, bound = b["invstd"]
     if count > 1:

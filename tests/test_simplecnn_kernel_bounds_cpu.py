@@ -22,11 +22,14 @@ worst-case bound of an n-term fp32 accumulation, 2 n u A, admits n ulps of A by 
 (289 terms for conv2, 224 pixel slots for a slab row), so 16 ulps cannot leave it; the fp32
 conv outputs are held by the dropped-tap, omitted-bias and skipped-row cases instead.
 """
+import functools
+
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+import elementwise
 from ddp_amd.ops import kernel_bounds as K
 from ddp_amd.ops import reference as R
 from ddp_amd.ops.kernel_bounds import U, acc_bound, bf16_store_bound, ratio, ratio_value
@@ -34,12 +37,7 @@ from ddp_amd.ops.kernel_bounds import U, acc_bound, bf16_store_bound, ratio, rat
 BF = torch.bfloat16
 SHAPES = [(1, 28, 28, 32, 64), (3, 28, 28, 32, 64), (2, 5, 7, 32, 64), (2, 6, 12, 32, 128), (2, 6, 12, 64, 64), (2, 6, 12, 64, 128), (2, 4, 40, 32, 64), (2, 12, 12, 32, 64)]
 DTS = [pytest.param(BF, id="bf16"), pytest.param(torch.float32, id="fp32")]
-
-
-def rnd(*shape, scale=1.0, seed=0, relu=False, dtype=BF):
-    g = torch.Generator().manual_seed(seed)
-    t = torch.randn(*shape, generator=g) * scale
-    return (torch.relu(t) if relu else t).to(dtype)
+rnd = functools.partial(elementwise.rnd, device="cpu")
 
 
 def nchw(t):

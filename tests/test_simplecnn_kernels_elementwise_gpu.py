@@ -44,8 +44,6 @@ Every output, slab and workspace is carved out of a larger buffer with sentinel 
 sides and pre-filled with NaN.  Run with -s for the KERN_RATIO <family> <shape> <error / bound>
 lines; profiles/simplecnn_kernels/README.md records the largest per family and shape.
 """
-import math
-
 import numpy as np
 import pytest
 import torch
@@ -53,47 +51,13 @@ import torch
 from ddp_amd.ops import kernel_bounds as K
 from ddp_amd.ops import reference as R
 from ddp_amd.ops.functional import fc_weight_frag
-from ddp_amd.ops.kernel_bounds import U, acc_bound, bf16_store_bound, ratio
+from ddp_amd.ops.kernel_bounds import acc_bound, bf16_store_bound, ratio
+from elementwise import BF, F32, SENTINEL, Guarded, U, bits, f64, n32, report_ratio, rnd
+from engine_step_cases import fold_terms, wgrad_nslot, wgrad_rows_of
 
 pytestmark = pytest.mark.gpu
 dev = "cuda"
-BF = torch.bfloat16
-F32 = torch.float32
-GUARD = 8192
-SENTINEL = 1152.0
-SENTINEL_U8 = 165
 LDS_MAX = 160 * 1024
-
-
-def rnd(*shape, scale=1.0, seed=0, relu=False, dtype=BF):
-    g = torch.Generator().manual_seed(seed)
-    t = torch.randn(*shape, generator=g) * scale
-    return (torch.relu(t) if relu else t).to(dtype).to(dev)
-
-
-class Guarded:
-    """A NaN-filled (or `fill`-ed) tensor between two sentinel bands of one allocation."""
-
-    def __init__(self, shape, dtype, fill=None):
-        n = math.prod(shape)
-        self.sent = SENTINEL_U8 if dtype == torch.uint8 else SENTINEL
-        self.buf = torch.full((n + 2 * GUARD,), self.sent, dtype=dtype, device=dev)
-        self.t = self.buf[GUARD:GUARD + n].view(shape)
-        self.t.fill_(float("nan") if fill is None else fill)
-        assert self.t.is_contiguous() and self.t.data_ptr() % 16 == 0
-
-    def check(self, what=""):
-        lo, hi = self.buf[:GUARD], self.buf[-GUARD:]
-        assert bool((lo == self.sent).all()) and bool((hi == self.sent).all()), f"write outside {what}"
-
-
-def f64(t):
-    return t.detach().cpu().double()
-
-
-def bits(t):
-    t = t.detach().cpu().contiguous()
-    return t.view(torch.int16 if t.dtype == BF else torch.int32)
 
 
 def out_bound(ref, E, dtype):
@@ -116,10 +80,6 @@ def wgrad_lds(W, Cin, Cout, Rr, es):
     Wp = (W + 7) & ~7
     nslot = (Rr * Wp + 31) // 32 * 32
     return es * (nslot * (Cout + 16) + (Rr + 2) * (Wp + 2) * (Cin + 16))
-
-
-def wgrad_nslot(W, Rr):
-    return (Rr * ((W + 7) & ~7) + 31) // 32 * 32
 
 
 # --------------------------------------------------------------------------- conv3x3 cases
@@ -324,23 +284,6 @@ def test_conv3x3_dgrad_fused_w1(C, B, H, W, pxt):
 
 
 # -------------------------------------------------------------------------- weight gradient
-def wgrad_rows64(dy, x, Rr):
-    """Float64 slab rows [B * nRC][Cout * 9 * Cin + Cout] of conv3x3_wgrad: image n, row chunk c."""
-    dy, x = f64(dy), f64(x)
-    B, H, W, Co = dy.shape
-    Ci = x.shape[3]
-    nRC = -(-H // Rr)
-    sh = [R._shift(x, kh - 1, kw - 1) for kh in range(3) for kw in range(3)]
-    rows = torch.zeros(B, nRC, Co * 9 * Ci + Co, dtype=torch.float64)
-    for c in range(nRC):
-        r0, r1 = c * Rr, min(H, (c + 1) * Rr)
-        d = dy[:, r0:r1]
-        dw = torch.stack([torch.einsum("nhwo,nhwi->noi", d, s[:, r0:r1]) for s in sh], 2)  # [B,Co,9,Ci]
-        rows[:, c, :Co * 9 * Ci] = dw.reshape(B, -1)
-        rows[:, c, Co * 9 * Ci:] = d.sum(dim=(1, 2))
-    return rows.reshape(B * nRC, -1)
-
-
 def run_wgrad(C, B, H, W, Cin, Cout, dtype, Rr, masked, family):
     es = 2 if dtype == BF else 4
     dy = rnd(B, H, W, Cout, scale=0.5, seed=140, dtype=dtype)
@@ -358,7 +301,7 @@ def run_wgrad(C, B, H, W, Cin, Cout, dtype, Rr, masked, family):
     C.conv3x3_wgrad(dy, yact if masked else None, x, slab.t, Rr)
     torch.cuda.synchronize()
     g = f64(dy) * (f64(yact) > 0) if masked else f64(dy)
-    ref, A = wgrad_rows64(g, x, Rr), wgrad_rows64(g.abs(), x.abs(), Rr)
+    ref, A = wgrad_rows_of(g, x, Rr), wgrad_rows_of(g.abs(), x.abs(), Rr)
     E = acc_bound(wgrad_nslot(W, Rr), A, dtype == F32)
     shape = (B, H, W, Cin, Cout, Rr)
     ratio(family + "_slab", shape, slab.t, ref, E, what)
@@ -527,13 +470,6 @@ def test_fc_bwd(C, B, mask, dtype):
         g_.check(what)
 
 
-def fold_terms(b, HW, CH):
-    """(block, slot) of every partial summed into image b's logits (common.h xent_logit_idx)."""
-    p0 = b * HW
-    kb0, kb1 = p0 // CH, (p0 + HW - 1) // CH
-    return [(kb0 + j, (0 if kb0 * CH == p0 else 1) if j == 0 else 0) for j in range(kb1 - kb0 + 1)]
-
-
 @pytest.mark.parametrize("with_idx", [False, True])
 @pytest.mark.parametrize("CH", [64, 128])
 @pytest.mark.parametrize("B", [1, 3, 7])
@@ -544,7 +480,7 @@ def test_xent_rows(C, B, CH, with_idx):
     part_h = torch.randn(nblk, 2, NO, generator=g0) * 0.7
     bias_h = torch.randn(NO, generator=g0) * 0.1
     bias_h[5] = bias_h[2]
-    terms = [fold_terms(b, HW, CH) for b in range(B)]
+    terms = [fold_terms(b, CH, HW) for b in range(B)]
     # row 0: logits about 30 apart; the last row: two tied maxima (exactly)
     k0, s0 = terms[0][0]
     part_h[k0, s0, 0] += 15.0
@@ -591,10 +527,6 @@ SGD_SETS = {
     "no_mbuf": [dict(mbuf=False)],
 }
 SGD_N = [1, 3, 4, 5, 1023, 4 * 256 * 2048 + 7]
-
-
-def n32(v):
-    return float(np.float32(v))
 
 
 @pytest.mark.parametrize("name", list(SGD_SETS))
@@ -748,7 +680,7 @@ def test_grad_reduce_single_segment(C, rows):
                     worst = max(worst, check_segment(dst.t, rows32, GR, scale, prior, what, "grad_reduce", (rows, n)))
                     dst.check(what)
                     slab.check(what)
-    print(f"KERN_RATIO grad_reduce_rows_max ({rows},) {worst:.4f}")
+    report_ratio(worst, "grad_reduce_rows_max", (rows,), tag="KERN_RATIO")
 
 
 @pytest.mark.parametrize("nseg", [1, 2, 6])

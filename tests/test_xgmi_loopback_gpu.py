@@ -23,13 +23,11 @@ import torch
 
 import xgmi_cases as X
 from ddp_amd.ops import kernel_bounds as K
+from elementwise import BF, F32, U, bits
+from elementwise import Guarded as _Guarded
 
 pytestmark = pytest.mark.gpu
 dev = "cuda"
-F32, BF = torch.float32, torch.bfloat16
-GUARD = 2048
-SENTINEL = 1152.0
-U = 2.0 ** -24
 WORLDS = list(range(1, X.MAX_RANKS + 1))
 SGD_OPTS = {
     "plain": dict(lr=0.05),
@@ -40,25 +38,8 @@ SGD_OPTS = {
 SCALES = (1.0, 1.0 / 3.0, 0.5)
 
 
-class Guarded:
-    """A NaN-filled tensor between two sentinel bands of one allocation."""
-
-    def __init__(self, n, dtype=F32, fill=float("nan")):
-        self.buf = torch.full((n + 2 * GUARD,), SENTINEL, dtype=dtype, device=dev)
-        self.t = self.buf[GUARD:GUARD + n]
-        self.t.fill_(fill)
-        assert self.t.data_ptr() % 16 == 0
-
-    def check(self, what):
-        lo, hi = self.buf[:GUARD], self.buf[GUARD + self.t.numel():]
-        assert bool((lo == SENTINEL).all()) and bool((hi == SENTINEL).all()), f"write outside {what}"
-
-
-def bits(t):
-    if isinstance(t, np.ndarray):
-        t = torch.from_numpy(np.ascontiguousarray(t))
-    t = t.detach().cpu().contiguous()
-    return t.view(torch.int16 if t.dtype == BF else torch.int32)
+def Guarded(n, dtype=F32, fill=None):  # (this file's bands are 2048 elements wide)
+    return _Guarded(n, dtype, fill, guard=2048)
 
 
 def same(a, b):
