@@ -203,18 +203,25 @@ def snap(v):
 
 
 class Recorder:
-    """A proxy around the native module that records the calls of ``KERNELS``."""
+    """A proxy around the native module that records the calls of ``kernels`` (None: ``KERNELS``).
+    ``outputs`` {name: f(a, kw) -> the tensors the call must write in full}: each is filled with
+    NaN before the launch, so that an element the kernel leaves unwritten shows in ``o``
+    (tests/simplecnn_step_cases.py: the Functions there allocate their outputs with torch.empty)."""
 
-    def __init__(self, native_module):
+    def __init__(self, native_module, kernels=None, outputs=None):
         self._native = native_module
+        self._kernels = KERNELS if kernels is None else kernels
+        self._outputs = outputs or {}
         self.trace = []
 
     def __getattr__(self, name):
         f = getattr(self._native, name)
-        if name not in KERNELS:
+        if name not in self._kernels:
             return f
 
         def call(*a, **kw):
+            for t in self._outputs[name](a, kw) if name in self._outputs else ():
+                t.fill_(float("nan"))
             pa, pk = snap(a), snap(kw)
             out = f(*a, **kw)
             self.trace.append(Call(name, pa, snap(a), pk, snap(kw)))
