@@ -359,6 +359,18 @@ __device__ __forceinline__ float wave_max(float v) {
   return fmaxf(fmaxf(lane_bcast(v, 0), lane_bcast(v, 16)), fmaxf(lane_bcast(v, 32), lane_bcast(v, 48)));
 }
 
+// The PAIR cross-entropy builds' target share of one class: keep * (ka + kb) (keep only with
+// smoothing), ka / kb the row's two weights where the class is y_a / y_b and 0 elsewhere.
+// Each operation rounds on its own (nothing contracts into the caller's subtraction), so
+// ka = 1, kb = 0 gives exactly the keep / 1 the builds without pair targets subtract.
+template <bool SMOOTH>
+__device__ __forceinline__ float xent_pair_share(float ka, float kb, XentSmooth<SMOOTH> sm) {
+#pragma clang fp contract(off)
+  const float k = ka + kb;
+  if constexpr (SMOOTH) return sm.keep * k;
+  else return k;
+}
+
 // Whole-batch softmax cross-entropy on one workgroup, fixed summation order.
 // part: the fused conv2+fc epilogue's partial logits, one pair of [NO] rows per conv
 // block of CH consecutive pixels of the flattened [B*HW] space: part[blk][slot][o],

@@ -231,6 +231,12 @@ struct GatherAffine {
 void image_gather_aug_nhwc4(const unsigned char* imgs, const long long* idx, const int* params, int B,
                             int H, int W, long N, const GatherAffine& aff, bool resample, bf16_t* out,
                             hipStream_t s);
+// the same with mixup / cutmix: mix [B][6] int32 on the device = (partner batch row, x1, y1, x2, y2,
+// bits of the fp32 weight wa); inside the box the partner's pixel, outside it the own pixel
+// (wa == 1) or fmaf(wa, own - partner, partner), both read through their own table rows
+void image_gather_mix_nhwc4(const unsigned char* imgs, const long long* idx, const int* params, const int* mix,
+                            int B, int H, int W, long N, const GatherAffine& aff, bool resample, bf16_t* out,
+                            hipStream_t s);
 void avgpool_fwd(const bf16_t* x, int N, int HW, int C, float* y, hipStream_t s);
 void avgpool_bwd(const float* dy, int N, int HW, int C, bf16_t* dx, hipStream_t s);
 // accum: C += alpha A.B (+ bias) instead of C =
@@ -320,11 +326,15 @@ void fc_bwd(const float* dL, const float* X, const float* Wf, float* dX, float* 
 // builds without smoothing, anything else their SMOOTH builds
 void xent(const float* part, int G, const float* bias, int C, int B, const long long* labels64,
           const int* labels32, BatchIdx bi, float* logits_out, float* dlogits, float* loss_out,
-          float* dbias, float gscale, float dbias_scale, hipStream_t s, float label_smoothing = 0.f);
+          float* dbias, float gscale, float dbias_scale, hipStream_t s, float label_smoothing = 0.f,
+          const long long* labels_b = nullptr, const float* pair_w = nullptr);
+// labels_b / pair_w (both or neither; int64 labels only): the PAIR builds - row b trains against
+// pair_w[b][0] * t(labels64[b]) + pair_w[b][1] * t(labels_b[b]), read from device memory
 
 // ResNet-width heads (C > 64, labels64, no bias fold): one wave per row; false if unsupported
 bool xent_wave_rows(const float* logits, int C, int B, const long long* labels, float* dlogits,
-                    float* loss_out, float gscale, hipStream_t s, float label_smoothing = 0.f);
+                    float* loss_out, float gscale, hipStream_t s, float label_smoothing = 0.f,
+                    const long long* labels_b = nullptr, const float* pair_w = nullptr);
 
 void xent_rows(const float* part, int HW, int CH, const float* bias, int NO, int B,
                const int* labels32, BatchIdx bi, float* dlogits, float* loss_rows, float gscale,

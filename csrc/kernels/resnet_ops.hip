@@ -557,17 +557,30 @@ __global__ void avgpool_bwd_kernel(const float* __restrict__ dy, int N, int HW, 
 // class order, then wave_sum: a fixed order), and one more subtraction per element; no extra
 // memory traffic.  SMOOTH = false is the kernel as it was: its XentSmooth is empty.
 constexpr int XR_M = 16;
-template <bool SMOOTH>
+// PAIR: the row trains against wa * t(y_a) + wb * t(y_b) (mixup / cutmix; t the smoothed one-hot),
+// y_b and (wa, wb) read from device memory.  k_c = wa [c == y_a] + wb [c == y_b] (both terms when
+// y_a == y_b) replaces the one-hot: dlogits_c = ((p_c - keep k_c) - eps_c) gscale and
+// loss = log(se) - [keep fmaf(wa, x_a - mx, wb (x_b - mx)) + eps_c S].  One more compare per
+// element and one more wave reduction per row.  PAIR = false is the kernel as it was.
+template <bool SMOOTH, bool PAIR>
 __global__ __launch_bounds__(256) void xent_wave_rows_kernel(const float* __restrict__ logits, int C,
                                                              int B, const long long* __restrict__ labels,
                                                              float* __restrict__ dlogits,
                                                              float* __restrict__ loss_out,
                                                              float* __restrict__ ws, int* __restrict__ ticket,
-                                                             float gscale, XentSmooth<SMOOTH> sm) {
+                                                             float gscale, XentSmooth<SMOOTH> sm,
+                                                             XentPair<PAIR> pr) {
   __shared__ int s_last;
   const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b < B) {
     const int label = (int)labels[b];
+    int label_b = -1;
+    float wa = 1.f, wb = 0.f;
+    if constexpr (PAIR) {
+      label_b = (int)pr.labels_b[b];
+      wa = pr.w[2 * b];
+      wb = pr.w[2 * b + 1];
+    }
     float x[XR_M];
     float mx = -INFINITY;
 #pragma unroll
@@ -577,11 +590,14 @@ __global__ __launch_bounds__(256) void xent_wave_rows_kernel(const float* __rest
       mx = fmaxf(mx, x[m]);
     }
     mx = wave_max(mx);
-    float se = 0.f, xl = 0.f, sx = 0.f;
+    float se = 0.f, xl = 0.f, xb = 0.f, sx = 0.f;
 #pragma unroll
     for (int m = 0; m < XR_M; ++m) {
       const int c = lane + 64 * m;
       if (c == label) xl = x[m];
+      if constexpr (PAIR) {
+        if (c == label_b) xb = x[m];
+      }
       if constexpr (SMOOTH) {
         if (c < C) sx += x[m] - mx;  // lanes / steps past C add exactly 0, not -inf
       }
@@ -590,12 +606,22 @@ __global__ __launch_bounds__(256) void xent_wave_rows_kernel(const float* __rest
     }
     se = wave_sum(se);
     xl = wave_sum(xl);  // logit[label]
+    if constexpr (PAIR) xb = wave_sum(xb);  // logit[label_b]
     if constexpr (SMOOTH) sx = wave_sum(sx);  // S = sum_c (x_c - mx)
     const float inv = 1.f / se;
 #pragma unroll
     for (int m = 0; m < XR_M; ++m) {
       const int c = lane + 64 * m;
-      if constexpr (SMOOTH) {
+      if constexpr (PAIR) {
+        // the target's share of class c, rounded on its own: the subtraction below then has the
+        // form of the builds without pair targets (wa = 1, wb = 0 gives their bits)
+        const float k = xent_pair_share(c == label ? wa : 0.f, c == label_b ? wb : 0.f, sm);
+        if constexpr (SMOOTH) {
+          if (c < C) dlogits[(long)b * C + c] = ((x[m] * inv - k) - sm.eps_c) * gscale;
+        } else {
+          if (c < C) dlogits[(long)b * C + c] = (x[m] * inv - k) * gscale;
+        }
+      } else if constexpr (SMOOTH) {
         if (c < C) dlogits[(long)b * C + c] = ((x[m] * inv - (c == label ? sm.keep : 0.f)) - sm.eps_c) * gscale;
       } else {
         if (c < C) dlogits[(long)b * C + c] = (x[m] * inv - (c == label ? 1.f : 0.f)) * gscale;
@@ -603,11 +629,13 @@ __global__ __launch_bounds__(256) void xent_wave_rows_kernel(const float* __rest
     }
     // log(se) - (xl - mx), not (mx + log(se)) - xl: the latter rounds at the logits' own
     // magnitude (an offset of 1e4 costs 5e-4 of the row's loss), xl - mx is (nearly) exact
+    float zt = xl - mx;  // the target's logit relative to the row maximum
+    if constexpr (PAIR) zt = fmaf(wa, xl - mx, wb * (xb - mx));
     if constexpr (SMOOTH) {
       // log(se) - [keep (xl - mx) + eps_c S]: every term relative to the row maximum, as above
-      if (lane == 0) st_wt(ws + b, __logf(se) - fmaf(sm.eps_c, sx, sm.keep * (xl - mx)));
+      if (lane == 0) st_wt(ws + b, __logf(se) - fmaf(sm.eps_c, sx, sm.keep * zt));
     } else {
-      if (lane == 0) st_wt(ws + b, __logf(se) - (xl - mx));
+      if (lane == 0) st_wt(ws + b, __logf(se) - zt);
     }
   }
   if (!last_arrival(ticket, gridDim.x, &s_last)) return;
@@ -659,26 +687,18 @@ __global__ __launch_bounds__(256) void image_gather_nhwc4_kernel(const unsigned 
 constexpr int GA_PX = 4;
 constexpr int GA_COLS = 5;
 
+// The source fetch of one run: the normalised fp32 values w[k][c] = fmaf(val, a_c, b_c) of output
+// pixels (r, c0 + k), k < GA_PX, of image n under its table row pr - everything up to the bf16
+// rounding, shared by the augmenting and the mixing kernel (which calls it once per source image).
+// RESAMPLE leaves w[k] at 0 for k >= npx; the integer build computes all four (columns past the
+// row read as padding).
 template <bool RESAMPLE>
-__global__ __launch_bounds__(256) void image_gather_aug_nhwc4_kernel(const unsigned char* __restrict__ imgs,
-                                                                     const long long* __restrict__ idx,
-                                                                     const int* __restrict__ params,
-                                                                     int H, int W, long N, int runs_per_row,
-                                                                     int blocks_per_image, GatherAffine aff,
-                                                                     bf16_t* __restrict__ out) {
-  const int b = blockIdx.x / blocks_per_image;
-  const int run = (blockIdx.x - b * blocks_per_image) * 256 + threadIdx.x;
-  if (run >= H * runs_per_row) return;
-  const int r = run / runs_per_row;
-  const int c0 = (run - r * runs_per_row) * GA_PX;
-  const int npx = min(GA_PX, W - c0);
-  long n = idx[b];
-  n = n < 0 ? 0 : (n >= N ? N - 1 : n);  // host validates; never read out of bounds
-  const int* pr = params + n * GA_COLS;
+__device__ __forceinline__ void ga_fetch(const unsigned char* __restrict__ imgs, const int* __restrict__ pr,
+                                         long n, int H, int W, long N, int r, int c0, int npx,
+                                         const GatherAffine& aff, float (&w)[GA_PX][3]) {
   const int top = pr[0], left = pr[1];
   const bool flip = pr[4] != 0;
   const long img = n * H * W * 3;  // byte offset of image n
-  uint2 o[GA_PX];
 
   if constexpr (!RESAMPLE) {
     const int sr = r + top;
@@ -720,10 +740,8 @@ __global__ __launch_bounds__(256) void image_gather_aug_nhwc4_kernel(const unsig
     }
 #pragma unroll
     for (int k = 0; k < GA_PX; ++k) {
-      float w[3];
 #pragma unroll
-      for (int c = 0; c < 3; ++c) w[c] = fmaf(flip ? v[GA_PX - 1 - k][c] : v[k][c], aff.a[c], aff.b[c]);
-      o[k] = pack4(w[0], w[1], w[2], 0.f);
+      for (int c = 0; c < 3; ++c) w[k][c] = fmaf(flip ? v[GA_PX - 1 - k][c] : v[k][c], aff.a[c], aff.b[c]);
     }
   } else {
     const int bh = pr[2], bw = pr[3];
@@ -739,23 +757,28 @@ __global__ __launch_bounds__(256) void image_gather_aug_nhwc4_kernel(const unsig
     const float ly = ys - (float)y0;
 #pragma unroll
     for (int k = 0; k < GA_PX; ++k) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) w[k][c] = 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < GA_PX; ++k) {
       if (k >= npx) break;
       const int cc = flip ? W - 1 - (c0 + k) : c0 + k;
       const float xs = fmaxf(fmaf((float)cc + 0.5f, sx, -0.5f), 0.f);
       const int x0 = min((int)xs, bw - 1), x1 = min(x0 + 1, bw - 1);
       const float lx = xs - (float)x0;
-      float w[3];
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
         const float v00 = tap(y0, x0, c), v01 = tap(y0, x1, c), v10 = tap(y1, x0, c), v11 = tap(y1, x1, c);
         const float t = fmaf(lx, v01 - v00, v00), bt = fmaf(lx, v11 - v10, v10);
-        w[c] = fmaf(fmaf(ly, bt - t, t), aff.a[c], aff.b[c]);
+        w[k][c] = fmaf(fmaf(ly, bt - t, t), aff.a[c], aff.b[c]);
       }
-      o[k] = pack4(w[0], w[1], w[2], 0.f);
     }
   }
+}
 
-  bf16_t* dst = out + (((long)b * H + r) * W + c0) * 4;
+// A run's four NHWC4 pixels out: two 16-byte stores when the run is whole and its base allows it
+__device__ __forceinline__ void ga_store(bf16_t* dst, const uint2 (&o)[GA_PX], int npx) {
   if (npx == GA_PX && ((unsigned long long)dst & 15ull) == 0) {
     reinterpret_cast<uint4*>(dst)[0] = make_uint4(o[0].x, o[0].y, o[1].x, o[1].y);
     reinterpret_cast<uint4*>(dst)[1] = make_uint4(o[2].x, o[2].y, o[3].x, o[3].y);
@@ -764,6 +787,96 @@ __global__ __launch_bounds__(256) void image_gather_aug_nhwc4_kernel(const unsig
     for (int k = 0; k < GA_PX; ++k)
       if (k < npx) reinterpret_cast<uint2*>(dst)[k] = o[k];
   }
+}
+
+template <bool RESAMPLE>
+__global__ __launch_bounds__(256) void image_gather_aug_nhwc4_kernel(const unsigned char* __restrict__ imgs,
+                                                                     const long long* __restrict__ idx,
+                                                                     const int* __restrict__ params,
+                                                                     int H, int W, long N, int runs_per_row,
+                                                                     int blocks_per_image, GatherAffine aff,
+                                                                     bf16_t* __restrict__ out) {
+  const int b = blockIdx.x / blocks_per_image;
+  const int run = (blockIdx.x - b * blocks_per_image) * 256 + threadIdx.x;
+  if (run >= H * runs_per_row) return;
+  const int r = run / runs_per_row;
+  const int c0 = (run - r * runs_per_row) * GA_PX;
+  const int npx = min(GA_PX, W - c0);
+  long n = idx[b];
+  n = n < 0 ? 0 : (n >= N ? N - 1 : n);  // host validates; never read out of bounds
+  float w[GA_PX][3];
+  ga_fetch<RESAMPLE>(imgs, params + n * GA_COLS, n, H, W, N, r, c0, npx, aff, w);
+  uint2 o[GA_PX];
+#pragma unroll
+  for (int k = 0; k < GA_PX; ++k) o[k] = pack4(w[k][0], w[k][1], w[k][2], 0.f);
+  ga_store(out + (((long)b * H + r) * W + c0) * 4, o, npx);
+}
+
+// The same gather with mixup / cutmix folded in (torchvision.transforms.v2 MixUp / CutMix after
+// the per-sample transforms): batch row b is mixed with batch row p = mix[b][0], both read through
+// their own images' rows of the parameter table.  mix[B][GM_COLS] int32 = (p, x1, y1, x2, y2, bits
+// of the fp32 weight wa), block-uniform like the rest.  With n_a / n_b the own / the partner's
+// normalised fp32 value, each exactly what the augmenting kernel rounds to bf16:
+//   inside the box (y1 <= r < y2, x1 <= c < x2, output coordinates): out = bf16(n_b)
+//   outside it: out = bf16(n_a) if wa == 1, else bf16(fmaf(wa, n_a - n_b, n_b))
+// so a cutmix batch and an unmixed batch (wa == 1) copy the augmenting gather's pixels of the
+// image each pixel comes from, and mixup (an empty box) blends.  A run fetches the partner only
+// when it needs it (it blends, or it overlaps the box) and its own image only when a pixel of
+// it lies outside the box; a run that straddles a box edge fetches both and selects per pixel.
+// The box is only ever compared against, the partner row is clamped: no table value can
+// move a read outside the images.
+constexpr int GM_COLS = 6;
+
+template <bool RESAMPLE>
+__global__ __launch_bounds__(256) void image_gather_mix_nhwc4_kernel(const unsigned char* __restrict__ imgs,
+                                                                     const long long* __restrict__ idx,
+                                                                     const int* __restrict__ params,
+                                                                     const int* __restrict__ mix, int B,
+                                                                     int H, int W, long N, int runs_per_row,
+                                                                     int blocks_per_image, GatherAffine aff,
+                                                                     bf16_t* __restrict__ out) {
+  const int b = blockIdx.x / blocks_per_image;
+  const int run = (blockIdx.x - b * blocks_per_image) * 256 + threadIdx.x;
+  if (run >= H * runs_per_row) return;
+  const int r = run / runs_per_row;
+  const int c0 = (run - r * runs_per_row) * GA_PX;
+  const int npx = min(GA_PX, W - c0);
+  const int* mr = mix + (long)b * GM_COLS;
+  int p = mr[0];
+  p = p < 0 ? 0 : (p >= B ? B - 1 : p);  // host validates; never read out of bounds
+  const int x1 = mr[1], y1 = mr[2], x2 = mr[3], y2 = mr[4];
+  const float wa = __int_as_float(mr[5]);
+  const bool in_rows = r >= y1 && r < y2;
+  const bool overlap = in_rows && c0 < x2 && c0 + npx > x1;   // a pixel of the run is inside the box
+  const bool inside = in_rows && c0 >= x1 && c0 + npx <= x2;  // every pixel of the run is
+  const bool blend = wa != 1.f;
+  float wo[GA_PX][3], wp[GA_PX][3];
+#pragma unroll
+  for (int k = 0; k < GA_PX; ++k) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) wo[k][c] = wp[k][c] = 0.f;
+  }
+  if (!inside) {
+    long n = idx[b];
+    n = n < 0 ? 0 : (n >= N ? N - 1 : n);
+    ga_fetch<RESAMPLE>(imgs, params + n * GA_COLS, n, H, W, N, r, c0, npx, aff, wo);
+  }
+  if (overlap || blend) {
+    long n = idx[p];
+    n = n < 0 ? 0 : (n >= N ? N - 1 : n);
+    ga_fetch<RESAMPLE>(imgs, params + n * GA_COLS, n, H, W, N, r, c0, npx, aff, wp);
+  }
+  uint2 o[GA_PX];
+#pragma unroll
+  for (int k = 0; k < GA_PX; ++k) {
+    const bool in_box = in_rows && c0 + k >= x1 && c0 + k < x2;
+    float v[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      v[c] = in_box ? wp[k][c] : (blend ? fmaf(wa, wo[k][c] - wp[k][c], wp[k][c]) : wo[k][c]);
+    o[k] = pack4(v[0], v[1], v[2], 0.f);
+  }
+  ga_store(out + (((long)b * H + r) * W + c0) * 4, o, npx);
 }
 
 // ---------------------------------------------------------------- small fp32 GEMM
@@ -1000,12 +1113,27 @@ void image_gather_aug_nhwc4(const unsigned char* imgs, const long long* idx, con
                        runs_per_row, blocks_per_image, aff, out);
 }
 
+void image_gather_mix_nhwc4(const unsigned char* imgs, const long long* idx, const int* params, const int* mix,
+                            int B, int H, int W, long N, const GatherAffine& aff, bool resample, bf16_t* out,
+                            hipStream_t s) {
+  const int runs_per_row = (W + GA_PX - 1) / GA_PX;
+  const int blocks_per_image = (H * runs_per_row + 255) / 256;
+  const dim3 grid((unsigned)((long)B * blocks_per_image));
+  if (resample)
+    hipLaunchKernelGGL(image_gather_mix_nhwc4_kernel<true>, grid, dim3(256), 0, s, imgs, idx, params, mix, B, H,
+                       W, N, runs_per_row, blocks_per_image, aff, out);
+  else
+    hipLaunchKernelGGL(image_gather_mix_nhwc4_kernel<false>, grid, dim3(256), 0, s, imgs, idx, params, mix, B, H,
+                       W, N, runs_per_row, blocks_per_image, aff, out);
+}
+
 void avgpool_fwd(const bf16_t* x, int N, int HW, int C, float* y, hipStream_t s) {
   hipLaunchKernelGGL(avgpool_fwd_kernel, dim3(N, C / 64), dim3(256), 0, s, x, N, HW, C, y);
 }
 
 bool xent_wave_rows(const float* logits, int C, int B, const long long* labels, float* dlogits,
-                    float* loss_out, float gscale, hipStream_t s, float label_smoothing) {
+                    float* loss_out, float gscale, hipStream_t s, float label_smoothing,
+                    const long long* labels_b, const float* pair_w) {
   constexpr int kMaxB = 8192;
   if (C > 64 * XR_M || B > kMaxB || B < 1) return false;
   static float* wsp[64] = {};
@@ -1013,14 +1141,22 @@ bool xent_wave_rows(const float* logits, int C, int B, const long long* labels, 
   RN_CHECK(hipGetDevice(&dev));
   dev &= 63;
   if (!wsp[dev]) RN_CHECK(hipMalloc(reinterpret_cast<void**>(&wsp[dev]), sizeof(float) * kMaxB));
-  // label_smoothing == 0 launches the build without smoothing: the kernel as it always was
-  if (label_smoothing != 0.f)
-    hipLaunchKernelGGL(xent_wave_rows_kernel<true>, dim3((B + 3) / 4), dim3(256), 0, s, logits, C, B, labels,
-                       dlogits, loss_out, wsp[dev], bn_ticket_slots(1), gscale,
-                       XentSmooth<true>{1.f - label_smoothing, label_smoothing / (float)C});
-  else
-    hipLaunchKernelGGL(xent_wave_rows_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, s, logits, C, B, labels,
-                       dlogits, loss_out, wsp[dev], bn_ticket_slots(1), gscale, XentSmooth<false>{});
+  // label_smoothing == 0 launches the build without smoothing and no pair targets the build
+  // without them: the kernel as it always was
+#define XR(SM, PR, smv, prv)                                                                                  \
+  hipLaunchKernelGGL((xent_wave_rows_kernel<SM, PR>), dim3((B + 3) / 4), dim3(256), 0, s, logits, C, B, labels, \
+                     dlogits, loss_out, wsp[dev], bn_ticket_slots(1), gscale, smv, prv)
+  const XentSmooth<true> sm{1.f - label_smoothing, label_smoothing / (float)C};
+  const XentPair<true> pr{labels_b, pair_w};
+  const bool pair = labels_b && pair_w;
+  if (label_smoothing != 0.f) {
+    if (pair) XR(true, true, sm, pr);
+    else XR(true, false, sm, XentPair<false>{});
+  } else {
+    if (pair) XR(false, true, XentSmooth<false>{}, pr);
+    else XR(false, false, XentSmooth<false>{}, XentPair<false>{});
+  }
+#undef XR
   return true;
 }
 

@@ -46,6 +46,18 @@ struct XentSmooth<true> {
   float keep, eps_c;
 };
 
+// Pair targets of the cross-entropy kernels' PAIR builds (mixup / cutmix): row b trains against
+// wa * t(labels[b]) + wb * t(labels_b[b]) with (wa, wb) = w[b][0..1].  Both come from device
+// memory, so a captured step follows a weight that changes every step.  The builds without
+// pair targets take the empty struct.
+template <bool PAIR>
+struct XentPair {};
+template <>
+struct XentPair<true> {
+  const long long* labels_b;  // int64 [B]
+  const float* w;             // fp32 [B][2]
+};
+
 // Source of SimpleCNN's first-layer activation when a kernel recomputes it on the fly
 // (a1 = relu(conv1(x0[idx])) / bf16) instead of reading a stored a1 tensor.
 struct C1Src {

@@ -201,8 +201,15 @@ def apply_fp32(images_u8: torch.Tensor, rows: torch.Tensor, affine: torch.Tensor
     plus a 24-bit addend of similar magnitude), so ``float64 -> float32 -> bf16`` reproduces the
     kernel's fma and rounding bit for bit.  Bilinear build: the module docstring's fp32
     formulas, operation for operation."""
+    return normalized_fp32(images_u8, rows, affine, resample).to(torch.bfloat16).float()
+
+
+def normalized_fp32(images_u8: torch.Tensor, rows: torch.Tensor, affine: torch.Tensor,
+                    resample: bool = False) -> torch.Tensor:
+    """:func:`apply_fp32` before its bf16 rounding: the float32 ``fmaf(val, a_c, b_c)`` the kernels
+    hold per value (what the mixing gather blends)."""
     if not resample:
-        return apply_reference(images_u8, rows, affine, False).to(torch.float32).to(torch.bfloat16).float()
+        return apply_reference(images_u8, rows, affine, False).to(torch.float32)
     images_u8, rows = images_u8.cpu(), rows.cpu().to(torch.int64)
     B, H, W, _ = images_u8.shape
     top, left, h, w = (rows[:, i:i + 1] for i in range(4))
@@ -222,4 +229,4 @@ def apply_fp32(images_u8: torch.Tensor, rows: torch.Tensor, affine: torch.Tensor
     t, bt = _fma(lx, v01 - v00, v00), _fma(lx, v11 - v10, v10)
     val = _fma(ly, bt - t, t)
     aff = affine.to(f32)
-    return _fma(val, aff[:, 0], aff[:, 1]).to(torch.bfloat16).float()
+    return _fma(val, aff[:, 0], aff[:, 1])

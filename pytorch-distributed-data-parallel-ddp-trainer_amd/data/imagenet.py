@@ -12,13 +12,15 @@ normalisation - like the reference's MNIST pipeline).  On the CPU the same data 
 out as NCHW float for the PyTorch oracle path.  Optionally the gather normalises
 (``DeviceImages(mean=, std=)``) and augments (``DeviceImageLoader(augment=)``: random crop
 with padding or random resized crop, horizontal flip - ``augment.py``) in the same pass,
-through the ``image_gather_aug_nhwc4`` kernel.
+through the ``image_gather_aug_nhwc4`` kernel, and mixes each batch with its rolled self
+(``DeviceImageLoader(mix=)``: mixup / cutmix - ``mix.py``) through ``image_gather_mix_nhwc4``.
 """
 from __future__ import annotations
 
 import torch
 
-from .augment import AugPlan, Augment, affine_table, apply_fp32
+from .augment import AugPlan, Augment, affine_table, apply_fp32, normalized_fp32
+from .mix import Mix, PairTarget, mix_fp32
 from .sampler import ShardedSampler, steps_per_epoch
 
 
@@ -78,13 +80,19 @@ class DeviceImages:
     def __len__(self) -> int:
         return self.images_u8.shape[0]
 
-    def gather(self, idx: torch.Tensor, plan: AugPlan | None = None):
+    def gather(self, idx: torch.Tensor, plan: AugPlan | None = None, mix: torch.Tensor | None = None):
         """GPU: ``(bf16 [B,H,W,4] NHWC4, int64 [B])``; CPU: ``(float32 [B,3,H,W], int64 [B])``.
         ``plan``: the epoch's augmentation table (rows indexed by the data-set index, on this
         device).  With a plan or a normalisation the augmenting kernel runs, and the CPU returns
         the values it stores (bf16-rounded; the integer build bit for bit); with neither, the
-        plain gather as before."""
+        plain gather as before.  ``mix``: the batch's int32 ``[B, 6]`` mixing table
+        (``mix.MixPlan.rows_for``, on this device): the mixing kernel runs, every row and its
+        partner read through their own rows of ``plan``; the CPU follows the kernel's fp32 order
+        (bit for bit where the batch copies pixels: cutmix and unmixed batches of the integer
+        build).  The labels returned are the batch's own."""
         y = self.labels.index_select(0, idx)
+        if mix is not None:
+            return self._gather_mixed(idx, plan, mix), y
         augmented = plan is not None or self.normalized
         if self.device.type == "cuda":
             from .. import native
@@ -107,13 +115,30 @@ class DeviceImages:
         return x, y
 
 
+    def _gather_mixed(self, idx, plan, mix):
+        plan = plan if plan is not None else self._identity_plan()
+        if self.device.type == "cuda":
+            from .. import native
+
+            n, h, w, _ = self.images_u8.shape
+            out = torch.empty(idx.numel(), h, w, 4, dtype=torch.bfloat16, device=self.device)
+            native.require().image_gather_mix_nhwc4(self.images_u8, idx, plan.rows, self.affine, mix, out,
+                                                    plan.resample)
+            return out
+        n32 = normalized_fp32(self.images_u8.index_select(0, idx), plan.rows.index_select(0, idx), self.affine,
+                              plan.resample)
+        return mix_fp32(n32, mix).permute(0, 3, 1, 2).contiguous()
+
+
 class DeviceImageLoader:
     """The rank's ``DistributedSampler``-exact batches out of device memory (ragged last
-    batch, drop_last=False), one index upload per epoch."""
+    batch, drop_last=False), one index upload per epoch.  With ``mix`` a batch is
+    ``(images, PairTarget)``: the mixed images and the two labels with their weights."""
 
     def __init__(self, data: DeviceImages, batch_size: int, world_size: int, rank: int,
-                 shuffle: bool = True, seed: int = 0, augment: Augment | None = None):
+                 shuffle: bool = True, seed: int = 0, augment: Augment | None = None, mix: Mix | None = None):
         self.data, self.batch_size, self.augment = data, int(batch_size), augment
+        self.mix = mix if mix is not None and mix.enabled else None
         self.sampler = ShardedSampler(len(data), world_size, rank, shuffle=shuffle, seed=seed)
 
     def __len__(self) -> int:
@@ -125,5 +150,15 @@ class DeviceImageLoader:
         if self.augment is not None:  # the epoch's table, uploaded once with the index list
             n, h, w, _ = self.data.images_u8.shape
             plan = self.augment.plan(self.sampler.epoch, n, h, w).to(self.data.device)
-        for s in range(0, idx.numel(), self.batch_size):
-            yield self.data.gather(idx[s:s + self.batch_size], plan)
+        if self.mix is None:
+            for s in range(0, idx.numel(), self.batch_size):
+                yield self.data.gather(idx[s:s + self.batch_size], plan)
+            return
+        n, h, w, _ = self.data.images_u8.shape
+        mplan = self.mix.plan(self.sampler.epoch, self.sampler.rank, len(self), h, w)
+        for step, s in enumerate(range(0, idx.numel(), self.batch_size)):
+            bidx = idx[s:s + self.batch_size]
+            table, wts = mplan.rows_for(step, bidx.numel())  # validated on the host, then uploaded
+            x, y = self.data.gather(bidx, plan, table.to(self.data.device))
+            yield x, PairTarget(y, y.index_select(0, table[:, 0].to(torch.int64).to(y.device)),
+                                wts.to(self.data.device))

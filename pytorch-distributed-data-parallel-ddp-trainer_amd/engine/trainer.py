@@ -101,6 +101,10 @@ class TrainOptions:
     aug_rrc: bool = False             # resnet18: random resized crop (ratio 3/4..4/3), bilinear
     aug_scale_min: float = 0.08       # aug_rrc: the smallest area share of the box
     aug_flip: bool = False            # resnet18: horizontal flip, p = 0.5, after the crop
+    mixup_alpha: float = 0.0          # resnet18: mixup with lam ~ Beta(a, a) per batch, in the gather (0: off)
+    cutmix_alpha: float = 0.0         # resnet18: cutmix with lam0 ~ Beta(a, a) per batch, in the gather (0: off)
+    mix_prob: float = 1.0             # probability that a batch is mixed at all
+    mix_switch_prob: float = 0.5      # with both alphas: probability that a mixed batch is a cutmix batch
 
 
 def validate_options(opts: TrainOptions):
@@ -149,6 +153,14 @@ def validate_options(opts: TrainOptions):
         raise ValueError("--normalize / --aug_crop_pad / --aug_rrc / --aug_flip run inside the image gather of "
                          "--model resnet18; simplecnn's MNIST loaders and the fused engine's in-kernel gather "
                          "have no augmenting build")
+    if not (opts.mixup_alpha >= 0.0 and opts.cutmix_alpha >= 0.0):
+        raise ValueError("--mixup_alpha and --cutmix_alpha must be >= 0 (0 = off)")
+    if not (0.0 <= opts.mix_prob <= 1.0 and 0.0 <= opts.mix_switch_prob <= 1.0):
+        raise ValueError("--mix_prob and --mix_switch_prob must lie in [0, 1]")
+    if opts.model != "resnet18" and uses_mix(opts):
+        raise ValueError("--mixup_alpha / --cutmix_alpha mix batches inside the image gather of --model resnet18 "
+                         "and train against pair targets; simplecnn's MNIST loaders have no mixing gather and "
+                         "the fused engine computes its loss from the data set's own labels")
     if opts.optimizer == "adamw" and opts.momentum != 0:
         raise ValueError("--momentum is SGD's; --optimizer adamw takes --beta1 / --beta2 / --adam_eps")
     if (opts.device or "").lower() == "gpu":  # the fused engine is certain: refuse before any process starts
@@ -176,6 +188,10 @@ def check_fused_engine_options(opts: TrainOptions, fused: bool):
         raise ValueError("--label_smoothing needs the module path (--engine module) or the CPU path; the "
                          "fused engine computes its loss inside the forward and fc_bwd kernels, which have "
                          "no smoothed build")
+    if fused and uses_mix(opts):
+        raise ValueError("--mixup_alpha / --cutmix_alpha need --model resnet18 (module path); the fused "
+                         "engine gathers its batch inside the forward kernel and reads the data set's own "
+                         "labels, which have no pair build")
     if fused and opts.optimizer == "lars":
         raise ValueError("--optimizer lars needs the module path (--engine module) or the CPU path; the "
                          "fused engine applies SGD inside the kernels that finish each gradient, before "
@@ -192,6 +208,21 @@ def uses_lr_schedule(opts: TrainOptions) -> bool:
 
 def uses_augment(opts: TrainOptions) -> bool:
     return bool(opts.normalize or opts.aug_crop_pad or opts.aug_rrc or opts.aug_flip)
+
+
+def uses_mix(opts: TrainOptions) -> bool:
+    return bool(opts.mixup_alpha or opts.cutmix_alpha)
+
+
+def build_mix(opts: TrainOptions):
+    """The run's Mix from the flags (None: both alphas 0) - a pure function of the flags and the
+    seed, so a resumed run redraws the same records."""
+    if not uses_mix(opts):
+        return None
+    from ..data.mix import Mix
+
+    return Mix(opts.mixup_alpha, opts.cutmix_alpha, prob=opts.mix_prob, switch_prob=opts.mix_switch_prob,
+               seed=opts.seed or 0)
 
 
 def build_augment(opts: TrainOptions):
@@ -279,7 +310,7 @@ def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
         norm = dict(mean=IMAGENET_MEAN, std=IMAGENET_STD) if opts.normalize else {}
         imgs, labels = synthetic_imagenet(opts.dataset_size, opts.image_size, opts.num_classes)
         loader = DeviceImageLoader(DeviceImages(imgs, labels, device, **norm), batch_size, world_size, rank,
-                                   augment=build_augment(opts))
+                                   augment=build_augment(opts), mix=build_mix(opts))
         sampler = loader.sampler
     elif on_gpu:
         imgs, labels, src = load_mnist(opts.data_root, opts.data)
@@ -643,7 +674,7 @@ def _run_module_epoch(model, loader, loss_fn, opt, device, log, log_every, max_s
     for batch_idx, batch in enumerate(loader):
         images, labels = batch if isinstance(batch, (tuple, list)) else tuple(batch)
         images = images.to(device, non_blocking=True)
-        labels = labels.to(device, non_blocking=True)
+        labels = labels.to(device, non_blocking=True)  # a PairTarget moves field by field
         if grad_accum == 1:
             opt.zero_grad()
         last = nb is not None and batch_idx + 1 >= nb
@@ -695,9 +726,11 @@ def _graph_cache(model) -> dict:
 def _run_graphed_epoch(model, loader, loss_fn, opt, log, log_every, max_steps):
     from .graph_step import GraphedStep
 
-    def step(x, y):
+    from ..data.mix import PairTarget
+
+    def step(x, *target):  # (y,) or a PairTarget's (y_a, y_b, w): every field a static input
         opt.zero_grad()
-        loss = loss_fn(model(x), y)
+        loss = loss_fn(model(x), PairTarget(*target) if len(target) == 3 else target[0])
         loss.backward()
         opt.step()
         return loss
@@ -706,15 +739,16 @@ def _run_graphed_epoch(model, loader, loss_fn, opt, log, log_every, max_steps):
     full = getattr(loader, "batch_size", None)  # the full batch: only that shape is captured
     n = 0
     for batch_idx, (images, labels) in enumerate(loader):
-        key = tuple(images.shape)
+        target = tuple(labels) if isinstance(labels, PairTarget) else (labels,)
+        key = tuple(images.shape) + (len(target),)
         if key not in graphs:
             if full is not None and images.shape[0] != full:
-                loss = step(images, labels)  # ragged tail: eager, no new capture
+                loss = step(images, *target)  # ragged tail: eager, no new capture
             else:
-                graphs[key] = GraphedStep(step, (images, labels), warmup=1)  # = this batch's step
+                graphs[key] = GraphedStep(step, (images, *target), warmup=1)  # = this batch's step
                 loss = graphs[key].warmup_out
         else:
-            loss = graphs[key](images, labels)
+            loss = graphs[key](images, *target)
         if batch_idx % log_every == 0:
             log(batch_idx, loss.item())
         n += 1
@@ -758,6 +792,8 @@ def _record_metrics(opts, rank, ws, epoch, nsteps, batch, dt, samples, ev=None, 
         rec["label_smoothing"] = opts.label_smoothing
     if uses_augment(opts):
         rec["augment"] = augment_tag(opts)
+    if uses_mix(opts):
+        rec["mix"] = build_mix(opts).describe()
     if ema_updates is not None:
         rec["ema_updates"] = ema_updates
     if clip is not None:

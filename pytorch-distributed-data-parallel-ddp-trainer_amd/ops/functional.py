@@ -9,7 +9,8 @@ conv1_relu           conv1_fwd (VALU, Cin=1, bias+ReLU fused)    conv1_wgrad (+R
 conv3x3_relu         conv3x3_fwd (MFMA, bias+ReLU fused)         conv3x3_dgrad (+mask), conv3x3_wgrad -> grad_reduce
 linear_nhwc          fc_partial + fc_reduce (split-K, fixed)     fc_bwd (dgrad+wgrad in one pass)
 cross_entropy        xent (softmax-xent fwd+bwd fused,           scale of the saved dlogits
-                     label smoothing by value)
+                     label smoothing by value, pair targets
+                     from device memory)
 ===================  ==========================================  ==============================
 
 Activations are NHWC in the compute dtype: bf16 (default; fp32 masters converted to bf16
@@ -148,7 +149,7 @@ class _LinearNHWC(torch.autograd.Function):
 
 class _CrossEntropy(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, labels, label_smoothing=0.0):
+    def forward(ctx, logits, labels, label_smoothing=0.0, labels_b=None, pair_w=None):
         B, C = logits.shape
         lg = logits.float().contiguous()
         dl = torch.empty_like(lg)
@@ -157,6 +158,10 @@ class _CrossEntropy(torch.autograd.Function):
         # (0: the ten-argument call as it always was, which an older build of the extension,
         # loaded as an A/B variant, also takes)
         kw = {"label_smoothing": float(label_smoothing)} if label_smoothing else {}
+        if labels_b is not None:
+            # pair targets (mixup / cutmix): the second label and the weights are read from device
+            # memory, so a captured step follows the weights its static inputs hold
+            kw.update(labels_b=labels_b.contiguous(), pair_w=pair_w.float().contiguous())
         _C().xent(lg, 1, None, labels.contiguous(), None, dl, loss, None, 1.0 / B, 0.0, **kw)
         ctx.save_for_backward(dl)
         return loss.reshape(())
@@ -164,7 +169,7 @@ class _CrossEntropy(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (dl,) = ctx.saved_tensors
-        return dl * g, None, None
+        return dl * g, None, None, None, None
 
 
 def conv1_relu(x, w, b, dtype=BF16):
@@ -180,7 +185,12 @@ def linear_nhwc(x, w, b, dtype=BF16):
 
 
 def cross_entropy(logits, labels, label_smoothing=0.0):
-    """Mean softmax cross-entropy; ``label_smoothing`` as torch's (eps / C over all C classes)."""
+    """Mean softmax cross-entropy; ``label_smoothing`` as torch's (eps / C over all C classes).
+    ``labels``: int64 ``[B]``, or a ``data.mix.PairTarget`` ``(y_a, y_b, w)`` for the loss
+    against ``w[:, 0] t(y_a) + w[:, 1] t(y_b)`` (the kernels' PAIR builds)."""
+    if isinstance(labels, tuple):
+        y_a, y_b, w = labels
+        return _CrossEntropy.apply(logits, y_a, label_smoothing, y_b, w)
     return _CrossEntropy.apply(logits, labels, label_smoothing)
 
 

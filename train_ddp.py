@@ -146,6 +146,17 @@ def parse_args(argv=None):
                    help="aug_rrc: the smallest share of the image area a box takes, in (0, 1]")
     p.add_argument("--aug_flip", action="store_true",
                    help="resnet18: horizontal flip with p = 0.5 after the crop, inside the gather kernel")
+    p.add_argument("--mixup_alpha", type=float, default=0.0, metavar="A",
+                   help="resnet18: mixup - each batch is blended with itself rolled by one row, lam ~ Beta(A, A) "
+                        "per batch, inside the gather kernel, and trains against the two labels' weighted "
+                        "(label-smoothed) targets inside the cross-entropy kernels (0 = off)")
+    p.add_argument("--cutmix_alpha", type=float, default=0.0, metavar="A",
+                   help="resnet18: cutmix - a box of area share 1 - lam0, lam0 ~ Beta(A, A) per batch, shows "
+                        "the rolled batch's pixels; the target weight follows the clipped area (0 = off)")
+    p.add_argument("--mix_prob", type=float, default=1.0, metavar="P",
+                   help="mixup / cutmix: the probability that a batch is mixed at all")
+    p.add_argument("--mix_switch_prob", type=float, default=0.5, metavar="P",
+                   help="with both alphas: the probability that a mixed batch is a cutmix batch")
     return p.parse_args(argv)
 
 
@@ -172,6 +183,8 @@ def main(argv=None):
                         eval_ema=a.eval_ema, label_smoothing=a.label_smoothing,
                         normalize=a.normalize, aug_crop_pad=a.aug_crop_pad, aug_rrc=a.aug_rrc,
                         aug_scale_min=a.aug_scale_min, aug_flip=a.aug_flip,
+                        mixup_alpha=a.mixup_alpha, cutmix_alpha=a.cutmix_alpha, mix_prob=a.mix_prob,
+                        mix_switch_prob=a.mix_switch_prob,
                         stall=tuple(float(v) for v in a.stall_at.split(":")) if a.stall_at else None,
                         fault=tuple(int(v) for v in a.fault_at.split(":")) if a.fault_at else None)
     validate_options(opts)
