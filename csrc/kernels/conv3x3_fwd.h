@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "kernels/conv3x3_body.h"
+#include "kernels/xent_body.h"
 
 namespace ddp_amd {
 

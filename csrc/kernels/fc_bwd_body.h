@@ -25,6 +25,7 @@
 #pragma once
 #include "kernels/common.h"
 #include "kernels/launchers.h"
+#include "kernels/xent_body.h"
 
 namespace ddp_amd {
 

@@ -25,6 +25,7 @@
 #include <stdexcept>
 
 #include "kernels/conv3x3_fwd.h"
+#include "kernels/xent_body.h"
 
 namespace ddp_amd {
 

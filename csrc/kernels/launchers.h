@@ -262,7 +262,7 @@ struct FcBwdExtras {
   const int* step_ctr = nullptr;
   // XENT: compute dL (softmax cross-entropy backward) in the prologue of every block
   // from the fused conv+fc partials [B][G][NO] instead of reading dL; loss_rows unused.
-  const float* part = nullptr;  // fused conv partials [blk][2][NO] (common.h xent_batch_block)
+  const float* part = nullptr;  // fused conv partials [blk][2][NO] (xent_body.h xent_batch_block)
   int HW = 0, CH = 0;           // image pixels, pixels per conv block
   const float* fc_bias = nullptr;
   const int* labels32 = nullptr;
@@ -330,11 +330,6 @@ void xent(const float* part, int G, const float* bias, int C, int B, const long 
           const long long* labels_b = nullptr, const float* pair_w = nullptr);
 // labels_b / pair_w (both or neither; int64 labels only): the PAIR builds - row b trains against
 // pair_w[b][0] * t(labels64[b]) + pair_w[b][1] * t(labels_b[b]), read from device memory
-
-// ResNet-width heads (C > 64, labels64, no bias fold): one wave per row; false if unsupported
-bool xent_wave_rows(const float* logits, int C, int B, const long long* labels, float* dlogits,
-                    float* loss_out, float gscale, hipStream_t s, float label_smoothing = 0.f,
-                    const long long* labels_b = nullptr, const float* pair_w = nullptr);
 
 void xent_rows(const float* part, int HW, int CH, const float* bias, int NO, int B,
                const int* labels32, BatchIdx bi, float* dlogits, float* loss_rows, float gscale,

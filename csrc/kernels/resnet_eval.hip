@@ -1,7 +1,7 @@
 // ResNet held-out evaluation: the folded BatchNorm vectors of the inference convolutions
 // (conv_infer.h), the per-image tail behind the classifier head and the running totals.
 //
-// Tail: one wave per row of fp32 logits, like xent_wave_rows_kernel, but for any class
+// Tail: one wave per row of fp32 logits, like xent_wave_rows_kernel (xent.hip), but for any class
 // count (the row is walked in 64-class steps, twice: maximum and label logit first, then
 // the sum of exponentials, the lowest index of the maximum and the label's rank).
 #include <stdexcept>
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void resnet_eval_tail_kernel(const float* __re
     // a NaN anywhere makes the row's maximum NaN (torch.max): no class equals it -> 0
     const int p = (nan || first >= C) ? 0 : first;
     pred[b] = p;
-    // log(se) - (xl - mx), as xent_wave_rows_kernel (xl - mx is nearly exact)
+    // log(se) - (xl - mx), as xent_row_loss, xent_body.h (xl - mx is nearly exact)
     loss[b] = __logf(se) - (xl - mx);
     correct[b] = (long long)p == lab64 ? 1 : 0;
     correct5[b] = before < 5 ? 1 : 0;

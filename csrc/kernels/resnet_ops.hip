@@ -547,105 +547,6 @@ __global__ void avgpool_bwd_kernel(const float* __restrict__ dy, int N, int HW, 
   dx[i] = f2bf(dy[(long)n * C + c] / (float)HW);
 }
 
-// ---------------------------------------------------------------- classifier loss
-// Mean softmax cross-entropy over [B][C] fp32 logits (C <= 1024) for wide heads: one wave
-// per row (4 rows per block, B/4 blocks) instead of one block looping over the rows.
-// Per-row losses go out write-through; the last block sums them in row order.
-// SMOOTH: label smoothing as torch's, target = keep * onehot + eps_c with keep = 1 - eps and
-// eps_c = eps / C (both rounded once on the host, by value: a captured step replays them).
-// One more wave reduction per row, S = sum_c (x_c - mx) over the C valid classes (per lane in
-// class order, then wave_sum: a fixed order), and one more subtraction per element; no extra
-// memory traffic.  SMOOTH = false is the kernel as it was: its XentSmooth is empty.
-constexpr int XR_M = 16;
-// PAIR: the row trains against wa * t(y_a) + wb * t(y_b) (mixup / cutmix; t the smoothed one-hot),
-// y_b and (wa, wb) read from device memory.  k_c = wa [c == y_a] + wb [c == y_b] (both terms when
-// y_a == y_b) replaces the one-hot: dlogits_c = ((p_c - keep k_c) - eps_c) gscale and
-// loss = log(se) - [keep fmaf(wa, x_a - mx, wb (x_b - mx)) + eps_c S].  One more compare per
-// element and one more wave reduction per row.  PAIR = false is the kernel as it was.
-template <bool SMOOTH, bool PAIR>
-__global__ __launch_bounds__(256) void xent_wave_rows_kernel(const float* __restrict__ logits, int C,
-                                                             int B, const long long* __restrict__ labels,
-                                                             float* __restrict__ dlogits,
-                                                             float* __restrict__ loss_out,
-                                                             float* __restrict__ ws, int* __restrict__ ticket,
-                                                             float gscale, XentSmooth<SMOOTH> sm,
-                                                             XentPair<PAIR> pr) {
-  __shared__ int s_last;
-  const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (b < B) {
-    const int label = (int)labels[b];
-    int label_b = -1;
-    float wa = 1.f, wb = 0.f;
-    if constexpr (PAIR) {
-      label_b = (int)pr.labels_b[b];
-      wa = pr.w[2 * b];
-      wb = pr.w[2 * b + 1];
-    }
-    float x[XR_M];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int m = 0; m < XR_M; ++m) {
-      const int c = lane + 64 * m;
-      x[m] = c < C ? logits[(long)b * C + c] : -INFINITY;
-      mx = fmaxf(mx, x[m]);
-    }
-    mx = wave_max(mx);
-    float se = 0.f, xl = 0.f, xb = 0.f, sx = 0.f;
-#pragma unroll
-    for (int m = 0; m < XR_M; ++m) {
-      const int c = lane + 64 * m;
-      if (c == label) xl = x[m];
-      if constexpr (PAIR) {
-        if (c == label_b) xb = x[m];
-      }
-      if constexpr (SMOOTH) {
-        if (c < C) sx += x[m] - mx;  // lanes / steps past C add exactly 0, not -inf
-      }
-      x[m] = c < C ? __expf(x[m] - mx) : 0.f;
-      se += x[m];
-    }
-    se = wave_sum(se);
-    xl = wave_sum(xl);  // logit[label]
-    if constexpr (PAIR) xb = wave_sum(xb);  // logit[label_b]
-    if constexpr (SMOOTH) sx = wave_sum(sx);  // S = sum_c (x_c - mx)
-    const float inv = 1.f / se;
-#pragma unroll
-    for (int m = 0; m < XR_M; ++m) {
-      const int c = lane + 64 * m;
-      if constexpr (PAIR) {
-        // the target's share of class c, rounded on its own: the subtraction below then has the
-        // form of the builds without pair targets (wa = 1, wb = 0 gives their bits)
-        const float k = xent_pair_share(c == label ? wa : 0.f, c == label_b ? wb : 0.f, sm);
-        if constexpr (SMOOTH) {
-          if (c < C) dlogits[(long)b * C + c] = ((x[m] * inv - k) - sm.eps_c) * gscale;
-        } else {
-          if (c < C) dlogits[(long)b * C + c] = (x[m] * inv - k) * gscale;
-        }
-      } else if constexpr (SMOOTH) {
-        if (c < C) dlogits[(long)b * C + c] = ((x[m] * inv - (c == label ? sm.keep : 0.f)) - sm.eps_c) * gscale;
-      } else {
-        if (c < C) dlogits[(long)b * C + c] = (x[m] * inv - (c == label ? 1.f : 0.f)) * gscale;
-      }
-    }
-    // log(se) - (xl - mx), not (mx + log(se)) - xl: the latter rounds at the logits' own
-    // magnitude (an offset of 1e4 costs 5e-4 of the row's loss), xl - mx is (nearly) exact
-    float zt = xl - mx;  // the target's logit relative to the row maximum
-    if constexpr (PAIR) zt = fmaf(wa, xl - mx, wb * (xb - mx));
-    if constexpr (SMOOTH) {
-      // log(se) - [keep (xl - mx) + eps_c S]: every term relative to the row maximum, as above
-      if (lane == 0) st_wt(ws + b, __logf(se) - fmaf(sm.eps_c, sx, sm.keep * zt));
-    } else {
-      if (lane == 0) st_wt(ws + b, __logf(se) - zt);
-    }
-  }
-  if (!last_arrival(ticket, gridDim.x, &s_last)) return;
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-    for (int r = 0; r < B; ++r) t += ld_agent(ws + r);
-    loss_out[0] = t / (float)B;
-  }
-}
-
 // ---------------------------------------------------------------- input pipeline
 // Device-resident uint8 RGB images [N][HW][3] + batch indices -> the stem's input:
 // NHWC bf16 [B][HW][4] = u8 / 255 with the 4th channel zero (one pixel per thread,
@@ -1129,35 +1030,6 @@ void image_gather_mix_nhwc4(const unsigned char* imgs, const long long* idx, con
 
 void avgpool_fwd(const bf16_t* x, int N, int HW, int C, float* y, hipStream_t s) {
   hipLaunchKernelGGL(avgpool_fwd_kernel, dim3(N, C / 64), dim3(256), 0, s, x, N, HW, C, y);
-}
-
-bool xent_wave_rows(const float* logits, int C, int B, const long long* labels, float* dlogits,
-                    float* loss_out, float gscale, hipStream_t s, float label_smoothing,
-                    const long long* labels_b, const float* pair_w) {
-  constexpr int kMaxB = 8192;
-  if (C > 64 * XR_M || B > kMaxB || B < 1) return false;
-  static float* wsp[64] = {};
-  int dev = 0;
-  RN_CHECK(hipGetDevice(&dev));
-  dev &= 63;
-  if (!wsp[dev]) RN_CHECK(hipMalloc(reinterpret_cast<void**>(&wsp[dev]), sizeof(float) * kMaxB));
-  // label_smoothing == 0 launches the build without smoothing and no pair targets the build
-  // without them: the kernel as it always was
-#define XR(SM, PR, smv, prv)                                                                                  \
-  hipLaunchKernelGGL((xent_wave_rows_kernel<SM, PR>), dim3((B + 3) / 4), dim3(256), 0, s, logits, C, B, labels, \
-                     dlogits, loss_out, wsp[dev], bn_ticket_slots(1), gscale, smv, prv)
-  const XentSmooth<true> sm{1.f - label_smoothing, label_smoothing / (float)C};
-  const XentPair<true> pr{labels_b, pair_w};
-  const bool pair = labels_b && pair_w;
-  if (label_smoothing != 0.f) {
-    if (pair) XR(true, true, sm, pr);
-    else XR(true, false, sm, XentPair<false>{});
-  } else {
-    if (pair) XR(false, true, XentSmooth<false>{}, pr);
-    else XR(false, false, XentSmooth<false>{}, XentPair<false>{});
-  }
-#undef XR
-  return true;
 }
 
 void avgpool_bwd(const float* dy, int N, int HW, int C, bf16_t* dx, hipStream_t s) {

@@ -40,9 +40,12 @@ struct BatchIdx {
 // eps_c = eps / C, each rounded once on the host.  The builds without smoothing take the
 // empty struct: no argument bytes they would have to skip.
 template <bool SMOOTH>
-struct XentSmooth {};
+struct XentSmooth {
+  static constexpr bool on = false;
+};
 template <>
 struct XentSmooth<true> {
+  static constexpr bool on = true;
   float keep, eps_c;
 };
 
@@ -51,9 +54,12 @@ struct XentSmooth<true> {
 // memory, so a captured step follows a weight that changes every step.  The builds without
 // pair targets take the empty struct.
 template <bool PAIR>
-struct XentPair {};
+struct XentPair {
+  static constexpr bool on = false;
+};
 template <>
 struct XentPair<true> {
+  static constexpr bool on = true;
   const long long* labels_b;  // int64 [B]
   const float* w;             // fp32 [B][2]
 };

@@ -11,25 +11,25 @@
 // (every 100 batches, reference train_ddp.py:201-202).
 // Labels come either from an int64 tensor or from the device-resident dataset
 // labels through the epoch index list (BatchIdx).
-#include "kernels/common.h"
+// Wide heads take xent_wave_rows_kernel; both kernels evaluate one row body (xent_body.h).
+#include "kernels/bn_tail.h"
 #include "kernels/launchers.h"
+#include "kernels/xent_body.h"
 
 #include <stdexcept>
+#include <string>
 
 namespace ddp_amd {
 
-constexpr int XE_MAXM = 16;  // up to 1024 classes
+static void xe_check(hipError_t e) {
+  if (e != hipSuccess) throw std::runtime_error(std::string("HIP: ") + hipGetErrorString(e));
+}
 
-// SMOOTH: label smoothing as torch's (the mass eps goes over all C classes, the true one
-// included): target = keep * onehot + eps_c, keep = 1 - eps and eps_c = eps / C rounded once
-// on the host and passed by value.  loss_b = log(se) - [keep (xl - mx) + eps_c S] with
-// S = sum_c (x_c - mx) over the valid classes (per lane in class order, then wave_sum),
-// dlogits = (softmax - keep * onehot - eps_c) * gscale; dbias sums those.  SMOOTH = false is
-// the kernel as it was (its XentSmooth is empty).
-// PAIR: pair targets (mixup / cutmix), row b against wa * t(y_a) + wb * t(y_b) with y_b and
-// (wa, wb) read from device memory; k_c = wa [c == y_a] + wb [c == y_b] replaces the one-hot in
-// dlogits, fmaf(wa, x_a - mx, wb (x_b - mx)) replaces xl - mx in the loss.  int64 labels only.
-// PAIR = false is the kernel as it was (its XentPair is empty).
+// The row arithmetic and what SMOOTH / PAIR mean: xent_body.h.  This kernel's own part: the
+// logits are the fixed-order sum of G partials plus the bias (with the optional logits_out
+// store), only M = ceil(C / 64) steps are walked (10 classes: one), every dlogits element is
+// also summed into dbias, each wave sums its rows' losses before the waves are summed; PAIR
+// takes int64 labels only.
 template <bool SMOOTH, bool PAIR>
 __global__ __launch_bounds__(1024) void xent_kernel(const float* __restrict__ part, int G,
                                                    const float* __restrict__ bias, int C, int B,
@@ -42,95 +42,40 @@ __global__ __launch_bounds__(1024) void xent_kernel(const float* __restrict__ pa
                                                    float dbias_scale, XentSmooth<SMOOTH> sm,
                                                    XentPair<PAIR> pr) {
   __shared__ float s_loss[16];
-  __shared__ float s_db[4][XE_MAXM * 64];  // dbias: 4 waves only (see xent())
+  __shared__ float s_db[4][XENT_M * 64];  // dbias: 4 waves only (see xent())
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
   const int M = (C + 63) / 64;
-  float db[XE_MAXM];
+  float db[XENT_M];
 #pragma unroll
-  for (int m = 0; m < XE_MAXM; ++m) db[m] = 0.f;
+  for (int m = 0; m < XENT_M; ++m) db[m] = 0.f;
   float lsum = 0.f;
   const int base = labels32 ? bi.base() : 0;
   for (int b = wave; b < B; b += nw) {
-    const int label = labels64 ? (int)labels64[b] : labels32[bi.row(b, base)];
-    int label_b = -1;
-    float wa = 1.f, wb = 0.f;
-    if constexpr (PAIR) {
-      label_b = (int)pr.labels_b[b];
-      wa = pr.w[2 * b];
-      wb = pr.w[2 * b + 1];
-    }
-    float x[XE_MAXM];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int m = 0; m < XE_MAXM; ++m) {
-      const int c = lane + 64 * m;
-      x[m] = -INFINITY;
-      if (m < M && c < C) {
-        float s = 0.f;
-        for (int g = 0; g < G; ++g) s += part[((long)b * G + g) * C + c];
-        x[m] = s + (bias ? bias[c] : 0.f);
-        if (logits_out) logits_out[(long)b * C + c] = x[m];
-        mx = fmaxf(mx, x[m]);
-      }
-    }
-    mx = wave_max(mx);
-    float se = 0.f, xl = 0.f, xb = 0.f, sx = 0.f;
-#pragma unroll
-    for (int m = 0; m < XE_MAXM; ++m) {
-      const int c = lane + 64 * m;
-      if (m < M && c < C) {
-        se += __expf(x[m] - mx);
-        if (c == label) xl = x[m];
-        if constexpr (PAIR) {
-          if (c == label_b) xb = x[m];
-        }
-        if constexpr (SMOOTH) sx += x[m] - mx;  // valid classes only: the rest add exactly 0
-      }
-    }
-    se = wave_sum(se);
-    xl = wave_sum(xl);
-    float zt = xl - mx;  // the target's logit relative to the row maximum
-    if constexpr (PAIR) {
-      xb = wave_sum(xb);
-      zt = fmaf(wa, xl - mx, wb * (xb - mx));
-    }
-    // log(se) - (xl - mx), not (mx + log(se)) - xl: the latter rounds at the logits' own
-    // magnitude (an offset of 1e4 costs 5e-4 of the row's loss), xl - mx is (nearly) exact
-    if constexpr (SMOOTH) {
-      sx = wave_sum(sx);  // S = sum_c (x_c - mx)
-      lsum += __logf(se) - fmaf(sm.eps_c, sx, sm.keep * zt);
-    } else {
-      lsum += __logf(se) - zt;
-    }
-    const float inv = 1.f / se;
-#pragma unroll
-    for (int m = 0; m < XE_MAXM; ++m) {
-      const int c = lane + 64 * m;
-      if (m < M && c < C) {
-        float d;
-        if constexpr (PAIR) {
-          // the target's share of class c, rounded on its own (common.h xent_pair_share)
-          const float k = xent_pair_share(c == label ? wa : 0.f, c == label_b ? wb : 0.f, sm);
-          if constexpr (SMOOTH) d = ((__expf(x[m] - mx) * inv - k) - sm.eps_c) * gscale;
-          else d = (__expf(x[m] - mx) * inv - k) * gscale;
-        } else if constexpr (SMOOTH)
-          d = ((__expf(x[m] - mx) * inv - (c == label ? sm.keep : 0.f)) - sm.eps_c) * gscale;
-        else
-          d = (__expf(x[m] - mx) * inv - (c == label ? 1.f : 0.f)) * gscale;
-        dlogits[(long)b * C + c] = d;
-        if constexpr (SMOOTH) {
+    const XentTarget t = xent_target(labels64 ? (int)labels64[b] : labels32[bi.row(b, base)], b, pr);
+    float* const drow = dlogits + (long)b * C;
+    float x[XENT_M];
+    const XentRow r = xent_row_stats<SMOOTH, PAIR>(x, C, M, lane, t, [&](int c) {
+      float s = 0.f;
+      for (int g = 0; g < G; ++g) s += part[((long)b * G + g) * C + c];
+      const float v = s + (bias ? bias[c] : 0.f);
+      if (logits_out) logits_out[(long)b * C + c] = v;
+      return v;
+    });
+    lsum += xent_row_loss<SMOOTH, PAIR>(r, t, sm);
+    xent_row_dlogits<SMOOTH, PAIR>(x, r, C, M, lane, t, sm, gscale, [&](int m, int c, float d) {
+      drow[c] = d;
+      if constexpr (SMOOTH) {
 #pragma clang fp contract(off)  // dbias: the in-order sum of the stored dlogits, bit for bit
-          db[m] += d;
-        } else {
-          db[m] += d;
-        }
+        db[m] += d;
+      } else {
+        db[m] += d;
       }
-    }
+    });
   }
   if (lane == 0) s_loss[wave] = lsum;
   if (dbias) {
 #pragma unroll
-    for (int m = 0; m < XE_MAXM; ++m)
+    for (int m = 0; m < XENT_M; ++m)
       if (m < M) s_db[wave][lane + 64 * m] = db[m];
   }
   __syncthreads();
@@ -145,8 +90,39 @@ __global__ __launch_bounds__(1024) void xent_kernel(const float* __restrict__ pa
       dbias[c] = (((s_db[0][c] + s_db[1][c]) + s_db[2][c]) + s_db[3][c]) * dbias_scale;
 }
 
+// Wide heads (64 < C <= 1024) over [B][C] fp32 logits: one wave per row (4 rows per block, B/4
+// blocks) instead of one block looping over the rows, a logit one global read, always XENT_M
+// steps.  Per-row losses go out write-through; the last block sums them in row order.
+template <bool SMOOTH, bool PAIR>
+__global__ __launch_bounds__(256) void xent_wave_rows_kernel(const float* __restrict__ logits, int C,
+                                                             int B, const long long* __restrict__ labels,
+                                                             float* __restrict__ dlogits,
+                                                             float* __restrict__ loss_out,
+                                                             float* __restrict__ ws, int* __restrict__ ticket,
+                                                             float gscale, XentSmooth<SMOOTH> sm,
+                                                             XentPair<PAIR> pr) {
+  __shared__ int s_last;
+  const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b < B) {
+    const XentTarget t = xent_target((int)labels[b], b, pr);
+    const float* const row = logits + (long)b * C;
+    float* const drow = dlogits + (long)b * C;
+    float x[XENT_M];
+    const XentRow r = xent_row_stats<SMOOTH, PAIR>(x, C, XENT_M, lane, t, [&](int c) { return row[c]; });
+    xent_row_dlogits<SMOOTH, PAIR>(x, r, C, XENT_M, lane, t, sm, gscale, [&](int, int c, float d) { drow[c] = d; });
+    const float loss = xent_row_loss<SMOOTH, PAIR>(r, t, sm);
+    if (lane == 0) st_wt(ws + b, loss);
+  }
+  if (!last_arrival(ticket, gridDim.x, &s_last)) return;
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+    for (int r = 0; r < B; ++r) t += ld_agent(ws + r);
+    loss_out[0] = t / (float)B;
+  }
+}
+
 // Engine variant (fusion level 0): one workgroup over the per-block partial logits
-// [blk][2][NO] written by the fused conv2 epilogue, see xent_batch_block (common.h).
+// [blk][2][NO] written by the fused conv2 epilogue, see xent_batch_block (xent_body.h).
 // Writes per-row loss and dlogits; the batch mean loss and the fc bias gradient are
 // finished by fc_bwd's first block (it holds dlogits).
 __global__ __launch_bounds__(1024) void xent_rows_kernel(const float* __restrict__ part, int HW, int CH,
@@ -168,6 +144,42 @@ void xent_rows(const float* part, int HW, int CH, const float* bias, int NO, int
                      bias, NO, B, labels32, bi, dlogits, loss_rows, gscale);
 }
 
+// Hands launch(sm, pr) the by-value arguments of one of the four builds: label_smoothing == 0
+// the build without smoothing, no pair targets the build without them (the kernels as they
+// always were).  keep and eps_c are each rounded once, here.
+template <typename F>
+static void xent_select_build(float label_smoothing, int C, const long long* labels_b, const float* pair_w,
+                              F launch) {
+  const XentSmooth<true> sm{1.f - label_smoothing, label_smoothing / (float)C};
+  const XentPair<true> pr{labels_b, pair_w};
+  const bool pair = labels_b && pair_w;
+  if (label_smoothing != 0.f) {
+    if (pair) launch(sm, pr);
+    else launch(sm, XentPair<false>{});
+  } else {
+    if (pair) launch(XentSmooth<false>{}, pr);
+    else launch(XentSmooth<false>{}, XentPair<false>{});
+  }
+}
+
+// ResNet-width heads (C > 64, labels64, no bias fold): one wave per row; false if unsupported
+static bool xent_wave_rows(const float* logits, int C, int B, const long long* labels, float* dlogits,
+                           float* loss_out, float gscale, hipStream_t s, float label_smoothing,
+                           const long long* labels_b, const float* pair_w) {
+  constexpr int kMaxB = 8192;
+  if (C > 64 * XENT_M || B > kMaxB || B < 1) return false;
+  static float* wsp[64] = {};
+  int dev = 0;
+  xe_check(hipGetDevice(&dev));
+  dev &= 63;
+  if (!wsp[dev]) xe_check(hipMalloc(reinterpret_cast<void**>(&wsp[dev]), sizeof(float) * kMaxB));
+  xent_select_build(label_smoothing, C, labels_b, pair_w, [&](auto sm, auto pr) {
+    hipLaunchKernelGGL((xent_wave_rows_kernel<decltype(sm)::on, decltype(pr)::on>), dim3((B + 3) / 4), dim3(256), 0,
+                       s, logits, C, B, labels, dlogits, loss_out, wsp[dev], bn_ticket_slots(1), gscale, sm, pr);
+  });
+  return true;
+}
+
 void xent(const float* part, int G, const float* bias, int C, int B, const long long* labels64,
           const int* labels32, BatchIdx bi, float* logits_out, float* dlogits, float* loss_out,
           float* dbias, float gscale, float dbias_scale, hipStream_t s, float label_smoothing,
@@ -181,21 +193,11 @@ void xent(const float* part, int G, const float* bias, int C, int B, const long 
       xent_wave_rows(part, C, B, labels64, dlogits, loss_out, gscale, s, label_smoothing, labels_b, pair_w))
     return;
   const int waves = dbias ? 4 : (B < 16 ? (B < 4 ? 4 : B) : 16);
-  // label_smoothing == 0 launches the build without smoothing and no pair targets the build
-  // without them: the kernel as it always was
-#define XE(SM, PR, smv, prv)                                                                                   \
-  hipLaunchKernelGGL((xent_kernel<SM, PR>), dim3(1), dim3(64 * waves), 0, s, part, G, bias, C, B, labels64,     \
-                     labels32, bi, logits_out, dlogits, loss_out, dbias, gscale, dbias_scale, smv, prv)
-  const XentSmooth<true> sm{1.f - label_smoothing, label_smoothing / (float)C};
-  const XentPair<true> pr{labels_b, pair_w};
-  if (label_smoothing != 0.f) {
-    if (pair) XE(true, true, sm, pr);
-    else XE(true, false, sm, XentPair<false>{});
-  } else {
-    if (pair) XE(false, true, XentSmooth<false>{}, pr);
-    else XE(false, false, XentSmooth<false>{}, XentPair<false>{});
-  }
-#undef XE
+  xent_select_build(label_smoothing, C, labels_b, pair_w, [&](auto sm, auto pr) {
+    hipLaunchKernelGGL((xent_kernel<decltype(sm)::on, decltype(pr)::on>), dim3(1), dim3(64 * waves), 0, s, part, G,
+                       bias, C, B, labels64, labels32, bi, logits_out, dlogits, loss_out, dbias, gscale,
+                       dbias_scale, sm, pr);
+  });
 }
 
 DDP_STAMPS_SETTER(stamps_set_xent)

@@ -208,7 +208,7 @@ def fold_block_partials(part: torch.Tensor, B: int, HW: int, CH: int) -> torch.T
 
     ``part`` is [blocks][2][NO]: block k covers pixels [k*CH, (k+1)*CH) of the flattened
     [B*HW] space; slot 0 belongs to the image of its first pixel, slot 1 to the next
-    image (csrc/kernels/common.h xent_batch_block).  Reference/test helper."""
+    image (csrc/kernels/xent_body.h xent_batch_block).  Reference/test helper."""
     nblk, _, NO = part.shape
     out = torch.zeros(B, NO, dtype=part.dtype, device=part.device)
     for k in range(nblk):

@@ -1,7 +1,8 @@
 """Inputs, a-priori bounds and a float32 emulation of the label-smoothed cross-entropy kernels
-(xent_wave_rows_kernel<true>, xent_kernel<true>), shared by tests/test_label_smoothing_cpu.py
-(whose docstring derives the bounds) and tests/test_label_smoothing_gpu.py.  Everything here
-runs on the CPU; nothing is calibrated on the kernels."""
+(xent_wave_rows_kernel<true>, xent_kernel<true>: csrc/kernels/xent_body.h), shared by
+tests/test_label_smoothing_cpu.py (whose docstring derives the bounds) and
+tests/test_label_smoothing_gpu.py.  Everything here runs on the CPU; nothing is calibrated on
+the kernels."""
 import math
 
 import torch

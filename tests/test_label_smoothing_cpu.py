@@ -10,8 +10,8 @@ Semantics (torch's): target = (1 - e) onehot(y) + e / C over all C classes, so
     loss_row  = logsumexp(x) - (1 - e) x_y - (e / C) sum_c x_c
     dlogits_c = (softmax_c - (1 - e) [c == y] - e / C) g
 
-The kernels (csrc/kernels/resnet_ops.hip xent_wave_rows_kernel<true>, csrc/kernels/xent.hip
-xent_kernel<true>) get keep = fl(1 - e) and ec = fl(e / C) by value (one rounding each; e is the
+The kernels (csrc/kernels/xent.hip xent_wave_rows_kernel<true> and xent_kernel<true>, one row
+body in csrc/kernels/xent_body.h) get keep = fl(1 - e) and ec = fl(e / C) by value (one rounding each; e is the
 float32 the binding narrows the double to, in the reference too) and evaluate, with mx the row
 maximum, se = sum exp(x_c - mx), S = sum_c (x_c - mx) over the C valid classes (per lane in
 class order, then wave_sum: at most M - 1 + 6 additions on any path, M = ceil(C / 64)):

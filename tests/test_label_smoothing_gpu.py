@@ -1,5 +1,5 @@
 """The SMOOTH builds of the cross-entropy kernels on MI355X (xent_wave_rows_kernel<true>,
-xent_kernel<true>; ``C.xent(..., label_smoothing=e)``), per element against the float64
+xent_kernel<true>, both csrc/kernels/xent.hip; ``C.xent(..., label_smoothing=e)``), per element against the float64
 reference within the a-priori bounds that tests/test_label_smoothing_cpu.py derives
 (tests/label_smoothing_cases.py computes them), and end to end through
 ``CrossEntropyLoss(label_smoothing=)``: SimpleCNN's module path against the CPU model, and

@@ -193,6 +193,30 @@ def test_pair_block_kernel_with_partials_bias_logits_and_dbias(C, E):
     assert torch.equal(bits(db), bits(want)), f"{what}: dbias is not the in-order sum of the stored dlogits"
 
 
+@pytest.mark.parametrize("NC", [65, 1000])
+@pytest.mark.parametrize("E", [0.0, 0.1])
+@pytest.mark.parametrize("pair", [False, True])
+def test_wave_and_block_kernels_agree(C, NC, E, pair):
+    """The same [5, NC] logits through xent_wave_rows_kernel (the plain call) and through
+    xent_kernel (the same call with logits_out and dbias, which routes there), in all four builds:
+    both evaluate the one row body of csrc/kernels/xent_body.h, so dlogits agree bit for bit.  The
+    mean losses are summed in different orders (rows in order; per wave, then over the waves), so
+    each is held to the loss bound of its build instead."""
+    B = 5
+    lg, ya, yb, w = (t.to(dev) for t in MC.pair_inputs(B, NC, 0.3))
+    tgt = (yb, w) if pair else (None, None)
+    what = f"wave / block xent {(B, NC)} E={E} pair={pair}"
+    dlw, lw, _, _ = run_xent(C, lg, ya, E, what + " wave", *tgt)
+    dlb, lb, _, _ = run_xent(C, lg, ya, E, what + " block", *tgt, extras=True)
+    assert torch.equal(bits(dlw), bits(dlb)), f"{what}: the two kernels' dlogits differ"
+    if pair:
+        loss_ref, _, bl, _ = MC.pair_bounds(lg, ya, yb, w, LS.f32(E), LS.f32(1.0 / B))
+    else:
+        loss_ref, _, bl, _ = LS.bounds(lg, ya, LS.f32(E), LS.f32(1.0 / B))
+    held("wave loss", lw, loss_ref, bl, what)
+    held("block loss", lb, loss_ref, bl, what)
+
+
 def test_xent_binding_checks_the_pair_arguments(C):
     B, NC = 3, 65
     lg, ya, yb, w = (t.to(dev) for t in MC.pair_inputs(B, NC, 0.3))
