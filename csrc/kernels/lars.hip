@@ -63,17 +63,12 @@
 #include "kernels/common.h"
 #include "kernels/flat_step.h"
 #include "kernels/launchers.h"
+#include "kernels/seg_finish.h"
 
 namespace ddp_amd {
 
 int seg_sqnorm_blocks(int n_items) {
   return n_items < 1 ? 1 : (n_items > LARS_MAX_BLOCKS ? LARS_MAX_BLOCKS : n_items);
-}
-
-__device__ __forceinline__ float2 ld_agent2(const float2* p) {
-  const unsigned long long v = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(p),
-                                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return make_float2(__uint_as_float((unsigned)v), __uint_as_float((unsigned)(v >> 32)));
 }
 
 // steps 1 and 2 for one quad: the squares of the elements below `left` (elements left in the
@@ -130,30 +125,16 @@ __global__ __launch_bounds__(LARS_THREADS) void seg_sqnorm_kernel(
   }
   if (!last_arrival(ticket, gridDim.x, &s_last)) return;
 
-  const int wave = t >> 6, lane = t & 63;
   const float coef = gscale ? gscale[0] : 1.f;
-  for (int s = wave; s < n_seg; s += 4) {
-    const LarsSeg sg = segs[s];
-    int ni = sg.n_items;
-    if (sg.item0 < 0 || ni < 0 || (long)sg.item0 + ni > n_items) ni = 0;
-    float aw = 0.f, ag = 0.f;
-    for (int k = lane; k < ni; k += 64) {
-      const float2 p = ld_agent2(partials + sg.item0 + k);
-      aw += p.x;
-      ag += p.y;
-    }
-    const float Sw = wave_sum(aw), Sg = wave_sum(ag);
-    if (lane == 0) {
-      const float wn = (float)sqrt((double)Sw);
-      float gn = (float)sqrt((double)Sg);
-      if (gscale) gn = __fmul_rn(gn, coef);
-      float ratio = 1.f;
-      if (sg.adapt && wn > 0.f && gn > 0.f)
-        ratio = __fdiv_rn(__fmul_rn(trust_coef, wn), __fadd_rn(fmaf(sg.wd, wn, gn), eps));
-      sums[s] = make_float2(Sw, Sg);
-      trust[s] = make_float4(ratio, sg.wd, wn, gn);
-    }
-  }
+  seg_finish(segs, n_seg, n_items, partials, sums, trust, [=](const LarsSeg& sg, float Sw, float Sg) {  // step 6
+    const float wn = (float)sqrt((double)Sw);
+    float gn = (float)sqrt((double)Sg);
+    if (gscale) gn = __fmul_rn(gn, coef);
+    float ratio = 1.f;
+    if (sg.adapt && wn > 0.f && gn > 0.f)
+      ratio = __fdiv_rn(__fmul_rn(trust_coef, wn), __fadd_rn(fmaf(sg.wd, wn, gn), eps));
+    return make_float4(ratio, sg.wd, wn, gn);
+  });
 }
 
 void seg_sqnorm(const float* w, const float* g, long n, const LarsItem* items, int n_items, const LarsSeg* segs,

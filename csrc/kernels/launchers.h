@@ -416,6 +416,20 @@ void seg_sqnorm(const float* w, const float* g, long n, const LarsItem* items, i
 void lars_step(float* p, const float* g, float* mbuf, long n, const SgdArgs& a, const ShadowSet& sh,
                const short* cmap, const float* trust, int n_seg, hipStream_t s, const float* gscale = nullptr,
                const float* lr_table = nullptr, int n_table = 0, SchedState* sched = nullptr);
+// ---- LAMB: Adam moments with per-tensor trust ratios |w| / |u| of the update (lamb.hip) ----
+// Pass 1: m' and v' stored; sums: 2 n_seg floats {S_w, S_u}; trust: 4 (n_seg + 1) floats
+// {phi, wd, |w|, |u|}; the segment table, partials and ticket are seg_sqnorm's.  coef: n_coef
+// entries {ibc1, bc2_sqrt, lr_t, 0} in device memory (16-byte aligned); the launch uses entry
+// min(sched->t, n_coef - 1) and leaves sched alone.  gscale as sgd_step.
+void lamb_moments(const float* w, const float* g, float* mbuf, float* vbuf, long n, const LarsItem* items, int n_items,
+                  const LarsSeg* segs, int n_seg, float* partials, int* ticket, float* sums, float* trust,
+                  const AdamArgs& a, const float* gscale, const float* coef, int n_coef, const SchedState* sched,
+                  hipStream_t s);
+// Pass 2: w' = fma(-(lr_t * phi), u, w) from the stored moments and trust[cmap[i / 64]], with the
+// shadow refresh; reads the same entry of coef and advances sched->t.  a.update == 0: shadows only.
+void lamb_step(float* p, const float* mbuf, const float* vbuf, long n, const AdamArgs& a, const ShadowSet& sh,
+               const short* cmap, const float* trust, int n_seg, const float* coef, int n_coef, SchedState* sched,
+               hipStream_t s);
 // ---- weight EMA (ema.hip) --------------------------------------------------------------
 // One update e' = fma(om, p - e, e) over the flat fp32 EMA buffer e and the live parameters p.
 // sched == nullptr: the constant-decay build, om by value, num_updates[0] += 1 (one int in

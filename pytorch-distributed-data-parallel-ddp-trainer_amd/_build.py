@@ -104,7 +104,11 @@ def _needs(obj: str, src: str, hdr_mtime: float, cmd=None) -> bool:
 # v_mov 0 + v_mov_dpp + add (the conv1 weight-gradient reduction of the dgrad role: 750 ->
 # 400 VALU instructions with the adds folded into v_add_f32_dpp)
 KERNEL_FLAGS = {"conv3x3.hip": ["-fno-slp-vectorize"], "conv3x3_bwd.hip": ["-fno-slp-vectorize"],
-                "infer.hip": ["-fno-slp-vectorize"]}  # (the forward body of conv3x3.hip)
+                "infer.hip": ["-fno-slp-vectorize"],  # (the forward body of conv3x3.hip)
+                # lamb.hip: no packed fp32 (v_pk_*_f32) selection.  Both kernels are bound by memory, so
+                # packed math buys nothing, and the scalar selection needs fewer VGPRs (52 / 80 against
+                # 58 / 82 for the apply / moments kernels; scratch-free either way: profiles/lamb/README.md)
+                "lamb.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 COMMON_FLAGS = ["-O3", "-fPIC", "-std=c++17", "-D__HIP_PLATFORM_AMD__"]
 DEVICE_FLAGS = ["-munsafe-fp-atomics"]
 BIND_FLAGS = ["-O2", "-DUSE_ROCM", "-DTORCH_EXTENSION_NAME=_C", "-DTORCH_API_INCLUDE_EXTENSION_H"]

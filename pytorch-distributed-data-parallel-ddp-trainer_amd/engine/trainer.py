@@ -32,7 +32,7 @@ from ..data import (DeviceImageLoader, DeviceImages, DeviceMNIST, DeviceMNISTLoa
                     load_mnist, synthetic_imagenet, synthetic_imagenet_test)
 from ..models import SimpleCNN, resnet18
 from ..models.layers import buffer_space, flat_space
-from ..ops import CrossEntropyLoss, FusedAdamW, FusedLARS, FusedSGD
+from ..ops import CrossEntropyLoss, FusedAdamW, FusedLAMB, FusedLARS, FusedSGD
 from ..parallel import DistributedDataParallel as DDP
 from ..parallel import cleanup, local_rank, native_comm, setup
 from ..utils.checkpoint import resume, resume_ema, save_checkpoint
@@ -85,13 +85,13 @@ class TrainOptions:
     lr_min: float = 0.0               # cosine / linear: the rate the decay ends at
     lr_step_epochs: int = 0           # step: multiply the rate by lr_gamma every N epochs
     lr_gamma: float = 0.1
-    optimizer: str = "sgd"            # sgd | adamw | lars (adamw, lars: module/CPU path)
-    beta1: float = 0.9                # adamw
-    beta2: float = 0.999              # adamw
-    adam_eps: float = 1e-8            # adamw
+    optimizer: str = "sgd"            # sgd | adamw | lars | lamb (all but sgd: module/CPU path)
+    beta1: float = 0.9                # adamw, lamb
+    beta2: float = 0.999              # adamw, lamb
+    adam_eps: float = 1e-8            # adamw, lamb
     trust_coef: float = 1e-3          # lars: the trust ratio's coefficient
     lars_eps: float = 1e-8            # lars: the trust ratio denominator's epsilon
-    lars_exclude: str = "1d"          # lars: 1d (BatchNorm scales, biases: ratio 1, no decay) | none
+    lars_exclude: str = "1d"          # lars / lamb: 1d (BatchNorm scales, biases: ratio 1, no decay) | none
     ema_decay: float = 0.0            # weight EMA updated by every optimizer step (0: off; module/CPU path)
     ema_warmup: bool = False          # decay_k = min(ema_decay, (1 + k) / (10 + k)) for update k
     eval_ema: bool = False            # every evaluation also evaluates the averaged weights
@@ -128,10 +128,10 @@ def validate_options(opts: TrainOptions):
         raise ValueError("--warmup_steps must be >= 0")
     if opts.lr_schedule == "step" and opts.lr_step_epochs < 1:
         raise ValueError("--lr_schedule step needs --lr_step_epochs N >= 1")
-    if opts.optimizer not in ("sgd", "adamw", "lars"):
-        raise ValueError(f"--optimizer must be sgd, adamw or lars, got {opts.optimizer!r}")
-    if opts.optimizer == "lars":
-        if not opts.trust_coef > 0 or opts.lars_eps < 0:
+    if opts.optimizer not in ("sgd", "adamw", "lars", "lamb"):
+        raise ValueError(f"--optimizer must be sgd, adamw, lars or lamb, got {opts.optimizer!r}")
+    if opts.optimizer in ("lars", "lamb"):
+        if opts.optimizer == "lars" and (not opts.trust_coef > 0 or opts.lars_eps < 0):
             raise ValueError("--trust_coef must be positive and --lars_eps >= 0")
         if opts.lars_exclude not in ("1d", "none"):
             raise ValueError(f"--lars_exclude must be 1d or none, got {opts.lars_exclude!r}")
@@ -161,8 +161,15 @@ def validate_options(opts: TrainOptions):
         raise ValueError("--mixup_alpha / --cutmix_alpha mix batches inside the image gather of --model resnet18 "
                          "and train against pair targets; simplecnn's MNIST loaders have no mixing gather and "
                          "the fused engine computes its loss from the data set's own labels")
-    if opts.optimizer == "adamw" and opts.momentum != 0:
-        raise ValueError("--momentum is SGD's; --optimizer adamw takes --beta1 / --beta2 / --adam_eps")
+    if opts.optimizer in ("adamw", "lamb") and opts.momentum != 0:
+        raise ValueError(f"--momentum is SGD's; --optimizer {opts.optimizer} takes --beta1 / --beta2 / --adam_eps")
+    if (opts.optimizer == "lamb" and opts.engine == "fused" and opts.model == "simplecnn"
+            and (opts.device or "").lower() != "cpu"):
+        # stricter than adamw / lars, which are refused here only with --device gpu: a lamb run names the
+        # path it takes, so a GPU found by --device auto never turns it into a late refusal in every rank
+        raise ValueError("--optimizer lamb needs the module path (--engine module), --model resnet18 or "
+                         "--device cpu: with --engine fused, SimpleCNN takes the fused engine wherever a GPU "
+                         "is found, and that engine has no LAMB")
     if (opts.device or "").lower() == "gpu":  # the fused engine is certain: refuse before any process starts
         check_fused_engine_options(opts, opts.engine == "fused" and opts.model == "simplecnn")
 
@@ -196,6 +203,10 @@ def check_fused_engine_options(opts: TrainOptions, fused: bool):
         raise ValueError("--optimizer lars needs the module path (--engine module) or the CPU path; the "
                          "fused engine applies SGD inside the kernels that finish each gradient, before "
                          "any tensor's gradient norm exists")
+    if fused and opts.optimizer == "lamb":
+        raise ValueError("--optimizer lamb needs the module path (--engine module) or the CPU path; the "
+                         "fused engine applies SGD inside the kernels that finish each gradient, before "
+                         "any tensor's update norm exists, and keeps no moment state")
     if fused and opts.optimizer != "sgd":
         raise ValueError("--optimizer adamw needs the module path (--engine module) or the CPU path; the "
                          "fused engine applies SGD inside the kernels that finish each gradient and keeps "
@@ -345,6 +356,11 @@ def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
         opt = FusedAdamW(model, lr=opts.lr, betas=(opts.beta1, opts.beta2), eps=opts.adam_eps,
                          weight_decay=opts.weight_decay, max_grad_norm=opts.clip_grad_norm or None,
                          lr_schedule=build_lr_schedule(opts, epochs, per_epoch))
+    elif opts.optimizer == "lamb":
+        opt = FusedLAMB(model, lr=opts.lr, betas=(opts.beta1, opts.beta2), eps=opts.adam_eps,
+                        weight_decay=opts.weight_decay, exclude=None if opts.lars_exclude == "none" else "1d",
+                        max_grad_norm=opts.clip_grad_norm or None,
+                        lr_schedule=build_lr_schedule(opts, epochs, per_epoch))
     elif opts.optimizer == "lars":
         opt = FusedLARS(model, lr=opts.lr, momentum=opts.momentum, weight_decay=opts.weight_decay,
                         trust_coef=opts.trust_coef, eps=opts.lars_eps,
@@ -364,7 +380,7 @@ def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
         print(f"Rank {rank}: No checkpoint found, starting from scratch.", flush=True)
     elif rank == 0:
         print(f"Rank {rank}: Resumed from {path}, starting at epoch {start_epoch}", flush=True)
-    if path is not None and opts.optimizer == "adamw":
+    if path is not None and opts.optimizer in ("adamw", "lamb"):
         # the Adam step is optimizer state: it came with the checkpoint, and is the schedule's index
         if opt.schedule_step() != start_epoch * per_epoch:
             print(f"Rank {rank}: WARNING: the checkpoint's optimizer step {opt.schedule_step()} is not "
@@ -471,7 +487,7 @@ def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
                         clip=opt.grad_clip_stats() if opts.metrics_json and rank == 0 else None,
                         lr=opt.current_lr() if opts.metrics_json and rank == 0 and opt.lr_schedule is not None
                         else None,
-                        trust=opt.trust_stats() if opts.metrics_json and rank == 0 and opts.optimizer == "lars"
+                        trust=opt.trust_stats() if opts.metrics_json and rank == 0 and opts.optimizer in ("lars", "lamb")
                         else None)
 
         if opts.verify_replicas and world_size > 1:
@@ -769,7 +785,7 @@ def _record_metrics(opts, rank, ws, epoch, nsteps, batch, dt, samples, ev=None, 
     """``samples``: images this rank processed in the epoch (:func:`samples_processed`);
     ``ev``: the epoch's evaluation totals, when it ran (eval_loss / eval_accuracy keys);
     ``clip``: FusedSGD.grad_clip_stats() with --clip_grad_norm (grad_norm: the last step's
-    norm; clipped_steps: steps clipped so far in this run); ``trust``: FusedLARS.trust_stats()
+    norm; clipped_steps: steps clipped so far in this run); ``trust``: FusedLARS / FusedLAMB.trust_stats()
     (trust_ratio_min / trust_ratio_max over the adapted tensors, the epoch's last step);
     ``ev_ema``: the evaluation totals of the averaged weights with --eval_ema (eval_ema_* keys);
     ``ema_updates``: WeightEMA.num_updates() with --ema_decay."""

@@ -8,6 +8,7 @@ import torch.nn.functional as F
 from . import reference
 from .adamw import FusedAdamW
 from .ema import WeightEMA
+from .lamb import FusedLAMB
 from .lars import FusedLARS
 from .lr_schedule import LRSchedule
 from .sgd import FusedSGD
@@ -43,4 +44,4 @@ class CrossEntropyLoss(nn.Module):
         return f"label_smoothing={self.label_smoothing}" if self.label_smoothing else ""
 
 
-__all__ = ["CrossEntropyLoss", "FusedAdamW", "FusedLARS", "FusedSGD", "LRSchedule", "WeightEMA", "reference"]
+__all__ = ["CrossEntropyLoss", "FusedAdamW", "FusedLAMB", "FusedLARS", "FusedSGD", "LRSchedule", "WeightEMA", "reference"]

@@ -135,7 +135,6 @@ class FusedAdamW(FlatOptimizer):
     # ------------------------------------------------------------------ API
     @torch.no_grad()
     def step(self):
-        g = self.param_groups[0]
         fs = self.flat
         self._prepare_grads()
         if self.exp_avg is None:  # (the first step: GraphedStep's warm-up, so before a capture)
@@ -144,17 +143,21 @@ class FusedAdamW(FlatOptimizer):
         if fs.params.is_cuda:
             from .. import native
 
-            shadows = self._all_shadows()
-            C = native.require()
-            gscale = self._gscale(C)
-            C.adamw(fs.params, fs.grads, self.exp_avg, self.exp_avg_sq, g["betas"][0], g["betas"][1],
-                    g["eps"], g["maximize"], True, shadows, gscale, self._sched_workspace())
+            self._step_native(native.require())
             fs.mark_bf16_fresh()
         else:
             self._step_torch()
         self.steps += 1
         if self.ema is not None:
             self.ema.update()
+
+    def _step_native(self, C):
+        g = self.param_groups[0]
+        fs = self.flat
+        shadows = self._all_shadows()
+        gscale = self._gscale(C)
+        C.adamw(fs.params, fs.grads, self.exp_avg, self.exp_avg_sq, g["betas"][0], g["betas"][1],
+                g["eps"], g["maximize"], True, shadows, gscale, self._sched_workspace())
 
     def _step_torch(self):
         """The kernel's operation sequence (adamw.hip) as fp32 torch ops, the scalars from the

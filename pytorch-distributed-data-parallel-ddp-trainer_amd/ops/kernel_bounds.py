@@ -441,3 +441,80 @@ def lars_reference(w, g, m, numels_begins, wds, adapts, lr, momentum, dampening,
         p_out[sl] = ww - lr * d3
         bp[sl] = (lr * e3 + U * lr * A3 + U * (np.abs(ww) + lr * A3)) * slack
     return p_out, m_out, np.asarray(ratios), bp, bm
+
+
+# ------------------------------------------------------------ LAMB: moments, update norm, trust ratio
+def lamb_reference(w, g, m, v, numels_begins, wds, adapts, lr, beta1, beta2, eps, ibc1=1.0, bc2_sqrt=1.0,
+                   maximize=False, coef=None, phis=None):
+    """The LAMB rule (ops/lamb.py) in float64 over flat float32 inputs, and the a-priori bounds of
+    the fp32 evaluation in lamb.hip's order.
+
+    ``numels_begins``: [(begin, numel)] per tensor; ``ibc1`` / ``bc2_sqrt`` / ``lr``: the step's
+    table entry; ``coef``: the fp32 clip coefficient or None; every scalar is taken at its
+    float32 value (w1 = fp32(1 - beta1), b2 = fp32(beta2), w2 = fp32(1 - beta2)).  ``phis``: the
+    trust ratios to apply (the device's own table) in place of the float64 ones - the parameter
+    bound then carries no ratio error.  Returns a dict: ``m, v, p`` (float64, flat; elements
+    outside every tensor keep their inputs), ``bm, bv, bp`` (their bounds), and per tensor ``wn,
+    un, phi`` with the relative bounds ``rel_wn, rel_un, rel_phi``.
+
+    Bounds, u = 2^-24, first order, times 1 + 2^-10 for the second-order terms:
+      d = coef g:                 ed = u |d|   (0 without clipping)
+      m' = fma(w1, d - m, m):     em = w1 (ed + u |d - m|) + u |m'|
+      v' = fma(w2 d, d, b2 v):    ev = w2 d^2 (u + 2 ed / |d|) + u |b2 v| + u |v'|
+      q = sqrt(v') / bc2_sqrt:    relative ev / (2 v') + 2 u (correctly rounded root, divide)
+      den = q + eps:              eden = q (ev / (2 v') + 2 u) + u den
+      r = (m' / den) ibc1:        er = (em + |m'| eden / den) ibc1 / den + 2 u |r|
+      u_ = fma(wd, w, r):         eu = er + u |u_|   (er without decay: u_ = r)
+      |w|: seg_sqnorm_chain k roundings of non-negative terms, gamma_k = k u / (1 - k u), halved
+        by the correctly rounded root plus its rounding: rel_wn = (gamma_k / 2 + u)(1 + gamma_k);
+      |u_|: the same, plus ||eu||_2 / ||u_||_2 for the error the summed elements carry
+        (triangle inequality);  phi = |w| / |u_|: rel_phi = rel_wn + rel_un + u
+      p' = fma(-(lr phi), u_, w): ep = lr phi eu + (rel_phi + u) lr phi |u_| + u (|w| + lr phi |u_|)
+    """
+    f64 = np.float64
+    w64, g64, m64, v64 = (np.asarray(x, dtype=np.float32).astype(f64) for x in (w, g, m, v))
+    lr, ep, i1, b2s = (f64(np.float32(x)) for x in (lr, eps, ibc1, bc2_sqrt))
+    w1, b2, w2 = f64(np.float32(1.0 - beta1)), f64(np.float32(beta2)), f64(np.float32(1.0 - beta2))
+    c = None if coef is None else f64(np.float32(coef))
+    slack = 1 + 2.0 ** -10
+    out = {"m": m64.copy(), "v": v64.copy(), "p": w64.copy()}
+    out.update({k: np.zeros_like(w64) for k in ("bm", "bv", "bp")})
+    for k in ("wn", "un", "phi", "rel_wn", "rel_un", "rel_phi"):
+        out[k] = np.zeros(len(numels_begins))
+    for s, ((b, n), wd, adapt) in enumerate(zip(numels_begins, wds, adapts)):
+        sl = slice(b, b + n)
+        ww, mm, vv = w64[sl], m64[sl], v64[sl]
+        wd = f64(np.float32(wd))
+        d = g64[sl] if c is None else g64[sl] * c
+        ed = 0.0 if c is None else U * np.abs(d)
+        if maximize:
+            d = -d
+        m1 = mm + w1 * (d - mm)
+        em = w1 * (ed + U * np.abs(d - mm)) + U * np.abs(m1)
+        v1 = w2 * d * d + b2 * vv
+        ev = w2 * (U * d * d + 2 * ed * np.abs(d)) + U * np.abs(b2 * vv) + U * np.abs(v1)
+        q = np.sqrt(v1) / b2s
+        rel_q = np.where(v1 > 0, ev / (2 * np.where(v1 > 0, v1, 1.0)), 0.0) + 2 * U
+        den = q + ep
+        eden = q * rel_q + U * den
+        r = m1 / den * i1
+        er = (em + np.abs(m1) * eden / den) * i1 / den + 2 * U * np.abs(r)
+        u_ = wd * ww + r
+        eu = er + (U * np.abs(u_) if wd != 0 else 0.0)
+        wn, un = np.sqrt((ww * ww).sum()), np.sqrt((u_ * u_).sum())
+        kch = seg_sqnorm_chain(n)
+        gk = kch * U / (1.0 - kch * U)
+        e_n = (gk / 2 + U) * (1 + gk)
+        rel_un = e_n + (np.sqrt((eu * eu).sum()) * slack / un if un > 0 else 0.0)
+        live = bool(adapt) and wn > 0 and un > 0
+        phi = wn / un if live else f64(1.0)
+        rel_phi = (e_n + rel_un + U) * slack if live else 0.0
+        for k, val in (("wn", wn), ("un", un), ("phi", phi), ("rel_wn", e_n), ("rel_un", rel_un), ("rel_phi", rel_phi)):
+            out[k][s] = val
+        if phis is not None:
+            phi, rel_phi = f64(np.float32(phis[s])), 0.0
+        a = lr * phi
+        out["m"][sl], out["v"][sl], out["p"][sl] = m1, v1, ww - a * u_
+        out["bm"][sl], out["bv"][sl] = em * slack, ev * slack
+        out["bp"][sl] = (a * eu + (rel_phi + U) * a * np.abs(u_) + U * (np.abs(ww) + a * np.abs(u_))) * slack
+    return out

@@ -67,30 +67,25 @@ def lars_layout(begins, numels, n: int, wds, adapts):
     return torch.from_numpy(segs), torch.from_numpy(items), torch.from_numpy(cmap)
 
 
-class FusedLARS(FusedSGD):
-    """``FusedSGD``'s momentum state, state-dict format and momentum step; its own gradient rule
-    (per-tensor decay and trust ratio) and kernels."""
+class SegmentTable:
+    """What the optimizers with per-tensor treatment (``FusedLARS``, ``FusedLAMB``) share, mixed in
+    ahead of their flat optimizer: which tensors are excluded, the segment table of the kernels,
+    the device workspace around it and the statistics read back from it.  The class sets
+    ``_norm_key`` (the name of the trust table's fourth column in ``trust_stats``) and its
+    ``__init__`` calls ``_init_segments``."""
 
-    _group_keys = (*_DEFAULTS, *_EXTRA)
+    _norm_key = "g_norm"
 
-    def __init__(self, model: torch.nn.Module, lr: float = 1e-3, momentum: float = 0.9, dampening: float = 0,
-                 weight_decay: float = 0, nesterov: bool = False, maximize: bool = False,
-                 trust_coef: float = 1e-3, eps: float = 1e-8, exclude="1d",
-                 max_grad_norm: float | None = None, lr_schedule=None):
-        if not trust_coef > 0:
-            raise ValueError("trust_coef must be positive")
-        if eps < 0 or weight_decay < 0:
-            raise ValueError("eps and weight_decay must be >= 0")
-        if not (exclude is None or exclude == "1d" or callable(exclude)):
-            raise ValueError("exclude must be '1d', None or a callable (name, shape) -> bool")
-        super().__init__(model, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
-                         nesterov=nesterov, maximize=maximize, max_grad_norm=max_grad_norm, lr_schedule=lr_schedule)
-        self.param_groups[0].update(trust_coef=trust_coef, eps=eps, exclude=exclude)
+    def _init_segments(self):
         self._excluded_wd = 0.0   # decay of the excluded tensors (0 by definition; the SGD-anchor test forces it)
         self._ws = None           # GPU: (plan, partials, ticket, sums, trust), allocated by the first step
-        self._host_stats = None   # CPU: float32 [n_seg, 4] {ratio, wd, wn, gn} of the last step
+        self._host_stats = None   # CPU: float32 [n_seg, 4] {ratio, wd, wn, norm} of the last step
 
-    # ------------------------------------------------------------------ segments
+    @staticmethod
+    def check_exclude(exclude):
+        if not (exclude is None or exclude == "1d" or callable(exclude)):
+            raise ValueError("exclude must be '1d', None or a callable (name, shape) -> bool")
+
     def excluded(self, name: str) -> bool:
         ex = self.param_groups[0]["exclude"]
         shape = self.flat.shapes[name]
@@ -128,11 +123,52 @@ class FusedLARS(FusedSGD):
                         torch.zeros(n_seg, 2, dtype=torch.float32, device=dev), trust.to(dev))
         return self._ws
 
-    def hyper_changed(self):
+    def _rewrite_segments(self):
         """weight_decay / exclude changed (a loaded state dict): rewrite the per-tensor
         coefficients in place - the layout depends on the shapes alone (never inside a capture)."""
         if self._ws is not None:
             self._ws[0][0].copy_(self.layout()[0])
+
+    def trust_stats(self) -> dict | None:
+        """Per parameter name ``{"w_norm", _norm_key, "ratio", "adapted"}`` of the last step; on the
+        GPU one device-to-host read.  ``None`` before the first step."""
+        if self._ws is not None:
+            t = self._ws[4][:-1].cpu().numpy()
+        elif self._host_stats is not None:
+            t = self._host_stats
+        else:
+            return None
+        adapts = self._seg_coefs()[1]
+        return {n: {"w_norm": float(t[s, 2]), self._norm_key: float(t[s, 3]), "ratio": float(t[s, 0]),
+                    "adapted": bool(adapts[s])} for s, n in enumerate(self.flat.names)}
+
+    def _load_group(self, saved: dict, keys):
+        # (a saved "callable" names no function: the constructor's exclude is kept)
+        super()._load_group(saved, [k for k in keys if k != "exclude" or saved.get(k) in (None, "1d")])
+
+
+class FusedLARS(SegmentTable, FusedSGD):
+    """``FusedSGD``'s momentum state, state-dict format and momentum step; its own gradient rule
+    (per-tensor decay and trust ratio) and kernels."""
+
+    _group_keys = (*_DEFAULTS, *_EXTRA)
+
+    def __init__(self, model: torch.nn.Module, lr: float = 1e-3, momentum: float = 0.9, dampening: float = 0,
+                 weight_decay: float = 0, nesterov: bool = False, maximize: bool = False,
+                 trust_coef: float = 1e-3, eps: float = 1e-8, exclude="1d",
+                 max_grad_norm: float | None = None, lr_schedule=None):
+        if not trust_coef > 0:
+            raise ValueError("trust_coef must be positive")
+        if eps < 0 or weight_decay < 0:
+            raise ValueError("eps and weight_decay must be >= 0")
+        self.check_exclude(exclude)
+        super().__init__(model, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                         nesterov=nesterov, maximize=maximize, max_grad_norm=max_grad_norm, lr_schedule=lr_schedule)
+        self.param_groups[0].update(trust_coef=trust_coef, eps=eps, exclude=exclude)
+        self._init_segments()
+
+    def hyper_changed(self):
+        self._rewrite_segments()
 
     # ------------------------------------------------------------------ the step
     def _step_native(self, C, first: bool):
@@ -172,19 +208,6 @@ class FusedLARS(FusedSGD):
         self._host_stats = stats
         return d
 
-    def trust_stats(self) -> dict | None:
-        """Per parameter name ``{"w_norm", "g_norm", "ratio", "adapted"}`` of the last step; on the
-        GPU one device-to-host read.  ``None`` before the first step."""
-        if self._ws is not None:
-            t = self._ws[4][:-1].cpu().numpy()
-        elif self._host_stats is not None:
-            t = self._host_stats
-        else:
-            return None
-        adapts = self._seg_coefs()[1]
-        return {n: {"w_norm": float(t[s, 2]), "g_norm": float(t[s, 3]), "ratio": float(t[s, 0]),
-                    "adapted": bool(adapts[s])} for s, n in enumerate(self.flat.names)}
-
     # ------------------------------------------------------------------ state
     def _group_values(self) -> dict:
         d = super()._group_values()
@@ -193,5 +216,5 @@ class FusedLARS(FusedSGD):
         return d
 
     def _load_group(self, saved: dict, keys):
-        super()._load_group(saved, [k for k in keys if k != "exclude" or saved.get(k) in (None, "1d")])
+        super()._load_group(saved, keys)
         self.hyper_changed()

@@ -44,20 +44,22 @@ def parse_args(argv=None):
     p.add_argument("--lr", type=float, default=0.01)
     p.add_argument("--momentum", type=float, default=0.0)
     p.add_argument("--weight_decay", type=float, default=0.0)
-    p.add_argument("--optimizer", choices=["sgd", "adamw", "lars"], default="sgd",
+    p.add_argument("--optimizer", choices=["sgd", "adamw", "lars", "lamb"], default="sgd",
                    help="sgd: torch.optim.SGD semantics (--momentum); adamw: torch.optim.AdamW semantics "
                         "(--beta1 / --beta2 / --adam_eps, decoupled --weight_decay), one fused kernel whose "
                         "bias correction follows a device step counter, so --graph_module replays are exact "
                         "(module/CPU path); lars: SGD with --momentum whose per-tensor decayed gradient is scaled "
                         "by a trust ratio computed on the device (--trust_coef / --lars_eps / --lars_exclude; "
-                        "module/CPU path)")
-    p.add_argument("--beta1", type=float, default=0.9, help="adamw: first-moment decay")
-    p.add_argument("--beta2", type=float, default=0.999, help="adamw: second-moment decay")
-    p.add_argument("--adam_eps", type=float, default=1e-8, help="adamw: the denominator's epsilon")
+                        "module/CPU path); lamb: AdamW's moments (--beta1 / --beta2 / --adam_eps) with --weight_decay "
+                        "inside the update and a per-tensor trust ratio |w| / |update| computed on the device "
+                        "(--lars_exclude; module/CPU path)")
+    p.add_argument("--beta1", type=float, default=0.9, help="adamw / lamb: first-moment decay")
+    p.add_argument("--beta2", type=float, default=0.999, help="adamw / lamb: second-moment decay")
+    p.add_argument("--adam_eps", type=float, default=1e-8, help="adamw / lamb: the denominator's epsilon")
     p.add_argument("--trust_coef", type=float, default=1e-3, help="lars: the trust ratio's coefficient")
     p.add_argument("--lars_eps", type=float, default=1e-8, help="lars: the trust ratio denominator's epsilon")
     p.add_argument("--lars_exclude", choices=["1d", "none"], default="1d",
-                   help="lars: 1d = parameters with ndim <= 1 (BatchNorm scales, biases) get ratio 1 and no "
+                   help="lars / lamb: 1d = parameters with ndim <= 1 (BatchNorm scales, biases) get ratio 1 and no "
                         "weight decay; none = every tensor is adapted and decayed")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--log_every", type=int, default=100)
