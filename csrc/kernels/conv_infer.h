@@ -26,6 +26,9 @@ void conv_gemm_infer(const ConvGeom& g, const ConvPlan& pl, const bf16_t* X, con
                      const InferEpi& ie, bf16_t* Y, float* part, hipStream_t s);
 void conv_halo_infer(const ConvGeom& g, int bp, int bc, int splits, const bf16_t* X, const bf16_t* Wt,
                      const InferEpi& ie, bf16_t* Y, float* part, hipStream_t s);
+// the pointwise family (conv_pw.hip): one launch, never split
+void conv_pw_infer(const PwPlan& pl, const bf16_t* X, const bf16_t* Wt, const InferEpi& ie, bf16_t* Y, long P,
+                   int Cin, int Cout, hipStream_t s);
 
 // sc = rsqrt(var + eps) * gamma, sh = fma(-mean, sc, beta) (bn_affine.h's definition)
 void bn_fold(const float* running_mean, const float* running_var, const float* gamma, const float* beta,

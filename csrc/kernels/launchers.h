@@ -197,6 +197,27 @@ void conv_gemm_wgrad(const ConvGeom& g, const bf16_t* dY, const bf16_t* X, float
 // whether conv_gemm_wgrad runs the halo kernel for this layer at this chunking
 bool conv_gemm_wgrad_uses_halo(const ConvGeom& g, int px_per_chunk);
 
+// ---- pointwise convolution as a direct GEMM (conv_pw.hip): 1x1 / s1 / p0, Cin and Cout
+// multiples of 64 up to 2048.  P = N*H*W pixels; X [P][Cin], W [Cout][Cin], Y [P][Cout].
+struct PwPlan {
+  int ok;  // 0: the channel counts are outside the family (every other field 0)
+  int bp, bc, grid_x, grid_y;  // block tile (pixels x channels); grid_x = BatchNorm stats slab rows
+};
+PwPlan conv_pw_plan(long P, int Cin, int Cout, int bp = 0, int bc = 0);  // bp / bc != 0: force a tile
+// stats != null: the training epilogue (slab [grid_x][2][Cout] for bn_finalize); aff: X is
+// raw, its producer's BatchNorm + ReLU is applied while staging
+void conv_pw_fwd(const PwPlan& pl, const bf16_t* X, const bf16_t* Wt, bf16_t* Y, float* stats, long P,
+                 int Cin, int Cout, const BnAffine* aff, hipStream_t s);
+struct PwWgradPlan {
+  int bm, bn;  // block tile (co x ci); 0: outside the family
+  int ppc, chunks;  // pixels per chunk, chunks = grid.z
+};
+PwWgradPlan conv_pw_wgrad_plan(long P, int Cin, int Cout, int bm = 0, int bn = 0, int ppc = 0);
+// one chunk: out = the gradient [Cout][Cin] (`accum` adds to it); several: out = slab
+// [chunks][Cout*Cin] for grad_reduce
+void conv_pw_wgrad(const PwWgradPlan& pl, const bf16_t* dY, const bf16_t* X, float* out, long P, int Cin,
+                   int Cout, bool accum, const BnAffine* aff, hipStream_t s);
+
 // ---- ResNet ops (resnet_ops.hip) -----------------------------------------------------
 int bn_finalize_groups(int rows);  // ws of bn_finalize: [groups][2][C]
 void bn_finalize(const float* slab, int rows, int C, float count, float eps, float momentum,

@@ -108,7 +108,12 @@ KERNEL_FLAGS = {"conv3x3.hip": ["-fno-slp-vectorize"], "conv3x3_bwd.hip": ["-fno
                 # lamb.hip: no packed fp32 (v_pk_*_f32) selection.  Both kernels are bound by memory, so
                 # packed math buys nothing, and the scalar selection needs fewer VGPRs (52 / 80 against
                 # 58 / 82 for the apply / moments kernels; scratch-free either way: profiles/lamb/README.md)
-                "lamb.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+                "lamb.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+                # conv_pw.hip: the same selection, kept scalar on purpose rather than for a gain: built with and
+                # without the flag the code object is the same today (no v_pk_*_f32 either way, at most 196
+                # VGPRs, no scratch), and the kernels are bound by MFMA and memory, so packed math in the
+                # epilogues or the staged affine could buy nothing if a later edit made the compiler pick it
+                "conv_pw.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 COMMON_FLAGS = ["-O3", "-fPIC", "-std=c++17", "-D__HIP_PLATFORM_AMD__"]
 DEVICE_FLAGS = ["-munsafe-fp-atomics"]
 BIND_FLAGS = ["-O2", "-DUSE_ROCM", "-DTORCH_EXTENSION_NAME=_C", "-DTORCH_API_INCLUDE_EXTENSION_H"]

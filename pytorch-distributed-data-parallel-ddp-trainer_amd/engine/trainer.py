@@ -30,7 +30,7 @@ import torch.distributed as dist
 
 from ..data import (DeviceImageLoader, DeviceImages, DeviceMNIST, DeviceMNISTLoader, get_dataloader,
                     load_mnist, synthetic_imagenet, synthetic_imagenet_test)
-from ..models import SimpleCNN, resnet18
+from ..models import SimpleCNN, resnet18, resnet50
 from ..models.layers import buffer_space, flat_space
 from ..ops import CrossEntropyLoss, FusedAdamW, FusedLAMB, FusedLARS, FusedSGD
 from ..parallel import DistributedDataParallel as DDP
@@ -67,7 +67,7 @@ class TrainOptions:
     grad_accum: int = 1               # micro-batches per optimizer step (module/CPU path)
     global_loss: bool = False         # log the all-reduced mean loss (module/CPU path, bug B14)
     pg_timeout_s: float | None = None
-    model: str = "simplecnn"          # simplecnn | resnet18 (BASELINE config 5)
+    model: str = "simplecnn"          # simplecnn | resnet18 (BASELINE config 5) | resnet50
     image_size: int = 224             # resnet18: synthetic image side
     num_classes: int = 1000           # resnet18
     dataset_size: int = 2048          # resnet18: synthetic images resident per rank
@@ -107,6 +107,15 @@ class TrainOptions:
     mix_switch_prob: float = 0.5      # with both alphas: probability that a mixed batch is a cutmix batch
 
 
+RESNETS = {"resnet18": resnet18, "resnet50": resnet50}
+
+
+def is_resnet(opts: TrainOptions) -> bool:
+    """The ResNet models share one path: synthetic ImageNet-shaped data, the module path on the
+    HIP ResNet Functions, every optimizer, augmentation, mixing and held-out evaluation."""
+    return opts.model in RESNETS
+
+
 def validate_options(opts: TrainOptions):
     """Option combinations that cannot run (checked by the CLI before any process starts, and
     by every rank)."""
@@ -114,10 +123,10 @@ def validate_options(opts: TrainOptions):
         raise ValueError("--eval_every must be >= 0 and --eval_batch_size >= 1")
     if opts.eval_size < 0:
         raise ValueError("--eval_size must be >= 0")
-    if opts.model == "resnet18" and (opts.eval_every or opts.eval_only) and not opts.eval_size:
+    if is_resnet(opts) and (opts.eval_every or opts.eval_only) and not opts.eval_size:
         raise ValueError("--eval_every / --eval_only evaluate SimpleCNN on the MNIST test split; the synthetic "
                          "ImageNet set of --model resnet18 has no held-out split unless --eval_size N builds one")
-    if opts.model != "resnet18" and opts.eval_size:
+    if not is_resnet(opts) and opts.eval_size:
         raise ValueError("--eval_size sizes the synthetic held-out split of --model resnet18; simplecnn's "
                          "split is the MNIST test set")
     if opts.clip_grad_norm < 0:
@@ -145,11 +154,11 @@ def validate_options(opts: TrainOptions):
         raise ValueError("--aug_crop_pad must be >= 0 (0 = off)")
     if opts.aug_crop_pad and opts.aug_rrc:
         raise ValueError("--aug_crop_pad and --aug_rrc are two crop modes: choose one")
-    if opts.aug_crop_pad >= opts.image_size and opts.model == "resnet18":
+    if opts.aug_crop_pad >= opts.image_size and is_resnet(opts):
         raise ValueError(f"--aug_crop_pad must be smaller than --image_size {opts.image_size}")
     if not 0.0 < opts.aug_scale_min <= 1.0:
         raise ValueError("--aug_scale_min must lie in (0, 1]")
-    if opts.model != "resnet18" and uses_augment(opts):
+    if not is_resnet(opts) and uses_augment(opts):
         raise ValueError("--normalize / --aug_crop_pad / --aug_rrc / --aug_flip run inside the image gather of "
                          "--model resnet18; simplecnn's MNIST loaders and the fused engine's in-kernel gather "
                          "have no augmenting build")
@@ -157,7 +166,7 @@ def validate_options(opts: TrainOptions):
         raise ValueError("--mixup_alpha and --cutmix_alpha must be >= 0 (0 = off)")
     if not (0.0 <= opts.mix_prob <= 1.0 and 0.0 <= opts.mix_switch_prob <= 1.0):
         raise ValueError("--mix_prob and --mix_switch_prob must lie in [0, 1]")
-    if opts.model != "resnet18" and uses_mix(opts):
+    if not is_resnet(opts) and uses_mix(opts):
         raise ValueError("--mixup_alpha / --cutmix_alpha mix batches inside the image gather of --model resnet18 "
                          "and train against pair targets; simplecnn's MNIST loaders have no mixing gather and "
                          "the fused engine computes its loss from the data set's own labels")
@@ -291,12 +300,12 @@ def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
 
     if opts.seed is not None:
         torch.manual_seed(opts.seed)  # B15: reproducible init (rank 0's weights win anyway)
-    if opts.model == "resnet18":
+    if is_resnet(opts):
         if on_gpu and opts.dtype != "bf16":
-            raise ValueError("resnet18 on the GPU runs bf16 MFMA kernels only (--dtype bf16)")
-        model = resnet18(num_classes=opts.num_classes).to(device)
+            raise ValueError(f"{opts.model} on the GPU runs bf16 MFMA kernels only (--dtype bf16)")
+        model = RESNETS[opts.model](num_classes=opts.num_classes).to(device)
         if on_gpu and opts.engine == "fused" and rank == 0:
-            print("Rank 0: resnet18 runs on the module path (the fused engine is SimpleCNN's)", flush=True)
+            print(f"Rank 0: {opts.model} runs on the module path (the fused engine is SimpleCNN's)", flush=True)
     elif opts.model == "simplecnn":
         if opts.dtype not in ("bf16", "fp32"):
             raise ValueError(f"--dtype must be bf16 or fp32, got {opts.dtype!r}")
@@ -315,7 +324,7 @@ def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
         fs = ddp_model.fs
     print(f"Rank {rank} model wrapped in DDP", flush=True)
 
-    if opts.model == "resnet18":
+    if is_resnet(opts):
         from ..data.augment import IMAGENET_MEAN, IMAGENET_STD
 
         norm = dict(mean=IMAGENET_MEAN, std=IMAGENET_STD) if opts.normalize else {}
@@ -332,7 +341,7 @@ def ddp_train(rank: int, world_size: int, epochs: int, batch_size: int,
         loader, sampler = get_dataloader(batch_size, world_size, rank, root=opts.data_root,
                                          source=opts.data, num_workers=opts.num_workers)
     edata = None
-    if (opts.eval_every or opts.eval_only) and opts.model == "resnet18":
+    if (opts.eval_every or opts.eval_only) and is_resnet(opts):
         timgs, tlabels = synthetic_imagenet_test(opts.eval_size, opts.image_size, opts.num_classes,
                                                  n_train=opts.dataset_size)
         edata, tsrc = DeviceImages(timgs, tlabels, device, **norm), "synthetic"  # evaluation never augments
@@ -508,7 +517,7 @@ def run_eval(model, engine, edata, device, opts, rank: int, world_size: int, fus
     from .evaluation import all_reduce_result, eval_shard, evaluate, evaluate_resnet
 
     idx = eval_shard(len(edata), world_size, rank)
-    if opts.model == "resnet18":  # GPU: the fused conv + BatchNorm inference path; CPU: the module forward
+    if is_resnet(opts):  # GPU: the fused conv + BatchNorm inference path; CPU: the module forward
         with _rank0_buffers(model, world_size):
             res = evaluate_resnet(model, edata, device, opts.eval_batch_size, idx, engine="fused")
     elif engine is not None:

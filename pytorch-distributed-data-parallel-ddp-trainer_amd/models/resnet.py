@@ -1,9 +1,10 @@
 """ResNet-18 (BASELINE.json config 5: synthetic 3x224x224, DDP stress of the bucketed
-all-reduce and the MFMA convolutions).
+all-reduce and the MFMA convolutions) and ResNet-50 (the model the large-batch ImageNet
+recipe of this trainer is written for).
 
-Module tree and ``state_dict`` names follow torchvision's ``resnet18`` (conv1, bn1,
-layer1..4 of BasicBlocks with ``downsample.0/1``, fc), so torchvision checkpoints
-load; conv weights live as native OHWI tensors (see layers.Conv2d).
+Module tree and ``state_dict`` names follow torchvision's ``resnet18`` / ``resnet50`` (conv1,
+bn1, layer1..4 of BasicBlocks or v1.5 Bottlenecks with ``downsample.0/1``, fc), so
+torchvision checkpoints load; conv weights live as native OHWI tensors (see layers.Conv2d).
 
 * CUDA input: NHWC bf16 pipeline on the HIP kernels of ``ops/resnet_fn.py`` -
   every conv is conv+BN(+residual)+ReLU fused into one autograd Function whose
@@ -89,8 +90,63 @@ class BasicBlock(nn.Module):
         return conv_bn_act_infer(out, self.conv2, folded[self.bn2], res=idt, relu=True, weight=w(self.conv2))
 
 
+class Bottleneck(nn.Module):
+    """torchvision's v1.5 bottleneck: 1x1 reduce, 3x3 (the stride is here), 1x1 expand x4."""
+    expansion = 4
+
+    def __init__(self, cin, width, stride=1):
+        super().__init__()
+        cout = width * self.expansion
+        self.conv1 = conv1x1(cin, width)
+        self.bn1 = nn.BatchNorm2d(width)
+        self.conv2 = conv3x3(width, width, stride)
+        self.bn2 = nn.BatchNorm2d(width)
+        self.conv3 = conv1x1(width, cout)
+        self.bn3 = nn.BatchNorm2d(cout)
+        self.relu = nn.ReLU(inplace=True)
+        self.downsample = None
+        if stride != 1 or cin != cout:
+            self.downsample = nn.Sequential(conv1x1(cin, cout, stride), nn.BatchNorm2d(cout))
+
+    def forward_nchw(self, x):
+        idt = x
+        out = self.relu(self.bn1(self.conv1.forward_nchw(x)))
+        out = self.relu(self.bn2(self.conv2.forward_nchw(out)))
+        out = self.bn3(self.conv3.forward_nchw(out))
+        if self.downsample is not None:
+            idt = self.downsample[1](self.downsample[0].forward_nchw(x))
+        return self.relu(out + idt)
+
+    def forward_hip(self, x):
+        from ..ops.resnet_fn import attach_stash, conv_bn_act
+
+        # the residual hand-over of BasicBlock.forward_hip; bn1 and bn2 are never stored:
+        # conv2's halo plan applies bn1 in its loads (another plan, e.g. a stride-2 conv2,
+        # materialises it), conv3's pointwise GEMM applies bn2 while staging
+        stash = attach_stash(x) if torch.is_grad_enabled() and x.requires_grad else None
+        out = conv_bn_act(x, self.conv1, self.bn1, relu=True, defer=True)
+        out = conv_bn_act(out, self.conv2, self.bn2, relu=True, defer=True)
+        if self.downsample is not None:
+            idt = conv_bn_act(x, self.downsample[0], self.downsample[1], relu=False, stash=stash)
+            return conv_bn_act(out, self.conv3, self.bn3, res=idt, relu=True)
+        return conv_bn_act(out, self.conv3, self.bn3, res=x, relu=True, stash=stash)
+
+    def forward_infer(self, x, folded):
+        """Evaluation forward, as :meth:`BasicBlock.forward_infer`: one fused launch per conv."""
+        from ..ops.resnet_fn import conv_bn_act_infer
+
+        w = folded.get
+        out = conv_bn_act_infer(x, self.conv1, folded[self.bn1], relu=True, weight=w(self.conv1))
+        out = conv_bn_act_infer(out, self.conv2, folded[self.bn2], relu=True, weight=w(self.conv2))
+        idt = x
+        if self.downsample is not None:
+            idt = conv_bn_act_infer(x, self.downsample[0], folded[self.downsample[1]], relu=False,
+                                    weight=w(self.downsample[0]))
+        return conv_bn_act_infer(out, self.conv3, folded[self.bn3], res=idt, relu=True, weight=w(self.conv3))
+
+
 class ResNet(nn.Module):
-    def __init__(self, layers=(2, 2, 2, 2), num_classes=1000):
+    def __init__(self, block=BasicBlock, layers=(2, 2, 2, 2), num_classes=1000):
         super().__init__()
         self.conv1 = Conv2d(3, 64, 7, stride=2, padding=3, bias=False)
         _init_conv(self.conv1)
@@ -98,16 +154,16 @@ class ResNet(nn.Module):
         self.relu = nn.ReLU(inplace=True)
         self.maxpool = nn.MaxPool2d(kernel_size=3, stride=2, padding=1)
         cin = 64
-        for i, (cout, n) in enumerate(zip((64, 128, 256, 512), layers)):
+        for i, (width, n) in enumerate(zip((64, 128, 256, 512), layers)):
             blocks = []
             for j in range(n):
                 stride = 2 if (j == 0 and i > 0) else 1
-                blocks.append(BasicBlock(cin, cout, stride))
-                cin = cout
+                blocks.append(block(cin, width, stride))
+                cin = width * block.expansion
             setattr(self, f"layer{i + 1}", nn.Sequential(*blocks))
         self.avgpool = nn.AdaptiveAvgPool2d((1, 1))
-        self.fc = Linear(512, num_classes)
-        bound = 1.0 / math.sqrt(512)
+        self.fc = Linear(cin, num_classes)
+        bound = 1.0 / math.sqrt(cin)
         with torch.no_grad():
             self.fc.weight.uniform_(-bound, bound)
             self.fc.bias.uniform_(-bound, bound)
@@ -166,4 +222,8 @@ class ResNet(nn.Module):
 
 
 def resnet18(num_classes: int = 1000) -> ResNet:
-    return ResNet((2, 2, 2, 2), num_classes)
+    return ResNet(BasicBlock, (2, 2, 2, 2), num_classes)
+
+
+def resnet50(num_classes: int = 1000) -> ResNet:
+    return ResNet(Bottleneck, (3, 4, 6, 3), num_classes)

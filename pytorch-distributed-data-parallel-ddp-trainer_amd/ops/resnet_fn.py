@@ -12,6 +12,10 @@ global_avgpool      avgpool_fwd                                       avgpool_bw
 linear_head         sgemm (in-tree fp32 GEMM, + bias)                 sgemm x3 (dx; dW and db accumulated in place)
 ==================  ================================================  ===========================================
 
+A 1x1 / s1 / p0 convolution with channel counts inside the pointwise family (ResNet-50's
+bottlenecks; none in ResNet-18) takes conv_pw_fwd / conv_pw_wgrad / conv_pw_infer instead of
+the conv_gemm forward, weight gradient and inference kernels (csrc/kernels/conv_pw.hip).
+
 Residual joins: a block's input x feeds its conv branch and its residual branch, so
 autograd would add the two gradients with a separate bf16 add kernel.  Instead the
 residual branch (``stash=``) parks its gradient in a :class:`GradStash` hung on x's
@@ -107,6 +111,16 @@ def _weight_bf16(w: torch.Tensor) -> torch.Tensor:
     return v if v is not None else w.detach().to(BF16).contiguous()
 
 
+def _pointwise(C, P, Cin, Cout, KH, KW, stride, pad):
+    """The BatchNorm stats-slab rows of conv_pw.hip's plan when the layer is in the pointwise
+    family (1x1 / s1 / p0, Cin and Cout multiples of 64 up to 2048), else None: every other
+    layer keeps its conv_gemm route (ResNet-18 has no such layer)."""
+    if KH != 1 or KW != 1 or stride != 1 or pad != 0:
+        return None
+    ok, _, _, rows = C.conv_pw_plan(P, Cin, Cout)
+    return rows if ok else None
+
+
 class _ConvBNAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, gamma, beta, running_mean, running_var, nbt, res, stride, pad, relu,
@@ -125,12 +139,18 @@ class _ConvBNAct(torch.autograd.Function):
         y = torch.empty(N, OH, OW, Cout, dtype=BF16, device=x.device)
         C = _C()
         P = N * OH * OW
-        _, _, splits, rows, _, halo = C.conv_gemm_plan(x, y, KH, KW, stride, pad)
+        xbn = getattr(x, "_ddp_amd_bn", None)
+        # a 1x1 / s1 / p0 layer inside the pointwise family is the plain GEMM of conv_pw.hip; a
+        # deferred input BatchNorm + ReLU stays deferred on it (forward and weight gradient)
+        pw = _pointwise(C, P, Cin, Cout, KH, KW, stride, pad)
+        if pw is not None:
+            splits, rows, halo = 1, pw, 0
+        else:
+            _, _, splits, rows, _, halo = C.conv_gemm_plan(x, y, KH, KW, stride, pad)
         # x may be the producer's deferred BatchNorm + ReLU (raw conv output + affine): the
         # halo forward and the halo weight gradient apply it while staging; any other plan
         # gets the activation materialised here
-        xbn = getattr(x, "_ddp_amd_bn", None)
-        if xbn is not None:
+        if xbn is not None and pw is None:
             ppc = C.conv_gemm_wgrad_ppc(x, y, KH, KW, stride, pad)
             if not (halo == 1 and C.conv_gemm_wgrad_uses_halo(x, y, KH, KW, stride, pad, ppc)):
                 xm = torch.empty_like(x)
@@ -141,7 +161,10 @@ class _ConvBNAct(torch.autograd.Function):
         if training:
             mean = torch.empty(Cout, device=x.device)
             invstd = torch.empty(Cout, device=x.device)
-        C.conv_gemm_fwd(x, wk, None, y, KH, KW, stride, pad, False, stats, part, bn=xbn)
+        if pw is not None:
+            C.conv_pw_fwd(x, wk, y, stats, bn=xbn)
+        else:
+            C.conv_gemm_fwd(x, wk, None, y, KH, KW, stride, pad, False, stats, part, bn=xbn)
         if training:
             ws = torch.empty(C.bn_finalize_groups(rows), 2, Cout, device=x.device)
             C.bn_finalize(stats, rows, Cout, float(P), eps, momentum, running_mean, running_var,
@@ -166,7 +189,7 @@ class _ConvBNAct(torch.autograd.Function):
         ctx.save_for_backward(x, wb, y, out if keep_out else None, mean, invstd)
         ctx.params = (w, gamma, beta)
         ctx.xbn = xbn
-        ctx.cfg = (stride, pad, bool(relu), res is not None, stem, P)
+        ctx.cfg = (stride, pad, bool(relu), res is not None, stem, P, pw is not None)
         # stash: this Function is the residual branch of a block; its gradient w.r.t. the
         # block input (res's for a join, x's for a downsample conv) goes to the stash
         ctx.stash = stash
@@ -176,7 +199,7 @@ class _ConvBNAct(torch.autograd.Function):
     def backward(ctx, dout):
         x, wb, y, out, mean, invstd = ctx.saved_tensors
         w, gamma, beta = ctx.params
-        stride, pad, relu, has_res, stem, P = ctx.cfg
+        stride, pad, relu, has_res, stem, P, pw = ctx.cfg
         C = _C()
         dout = dout.to(BF16).contiguous()
         Cout, KH, KW, wcin = w.shape
@@ -210,15 +233,25 @@ class _ConvBNAct(torch.autograd.Function):
         # weight gradient
         gw = direct_grad.grad_dst(w)
         acc_w = gw is not None and direct_grad.accumulate(w)
-        ppc = C.conv_gemm_wgrad_ppc(x, dy, KH, KW, stride, pad)
-        chunks = C.conv_gemm_wgrad_chunks(x, dy, KH, KW, stride, pad, ppc)
         row = w.numel()
         dw = gw if gw is not None else torch.empty(w.shape, device=dev)
+        if pw:
+            chunks = C.conv_pw_wgrad_plan(P, x.shape[-1], Cout)[3]
+        else:
+            ppc = C.conv_gemm_wgrad_ppc(x, dy, KH, KW, stride, pad)
+            chunks = C.conv_gemm_wgrad_chunks(x, dy, KH, KW, stride, pad, ppc)
+
+        def wgrad(dst, acc):  # dst: the gradient itself (one chunk) or the slab
+            if pw:
+                C.conv_pw_wgrad(dy, x, dst, acc, bn=ctx.xbn)
+            else:
+                C.conv_gemm_wgrad(dy, x, dst, KH, KW, stride, pad, ppc, acc, bn=ctx.xbn)
+
         if chunks == 1:
-            C.conv_gemm_wgrad(dy, x, dw, KH, KW, stride, pad, ppc, acc_w, bn=ctx.xbn)
+            wgrad(dw, acc_w)
         else:
             slab = torch.empty(chunks, row, device=dev)
-            C.conv_gemm_wgrad(dy, x, slab, KH, KW, stride, pad, ppc, False, bn=ctx.xbn)
+            wgrad(slab, False)
             C.grad_reduce([(slab, row, 0, row, chunks, dw.view(-1), 1.0, acc_w)])
         rw = None if gw is not None else dw
         rg, rb = (None, None) if direct_bn else (dgamma, dbeta)
@@ -396,10 +429,13 @@ def conv_bn_act_infer(x, conv, bn_folded, res=None, relu=True, weight=None):
     wk = weight if weight is not None else conv_weight_infer(conv)
     y = torch.empty(N, OH, OW, Cout, dtype=BF16, device=x.device)
     C = _C()
+    rs = res.contiguous() if res is not None else None
+    if _pointwise(C, y.numel() // Cout, Cin, Cout, KH, KW, stride, pad) is not None:
+        C.conv_pw_infer(x, wk, sc, sh, rs, y, bool(relu))
+        return y
     _, _, splits, _, _, _ = C.conv_gemm_plan(x, y, KH, KW, stride, pad)
     part = torch.empty(splits * y.numel(), device=x.device) if splits > 1 else None
-    C.conv_gemm_infer(x, wk, sc, sh, res.contiguous() if res is not None else None, y, KH, KW, stride, pad,
-                      bool(relu), part)
+    C.conv_gemm_infer(x, wk, sc, sh, rs, y, KH, KW, stride, pad, bool(relu), part)
     return y
 
 

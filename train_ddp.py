@@ -100,8 +100,9 @@ def parse_args(argv=None):
                    help="log the all-reduced mean loss instead of rank 0's local loss (module/CPU path)")
     p.add_argument("--pg_timeout_min", type=float, default=30.0,
                    help="process-group timeout in minutes (reference default 30)")
-    p.add_argument("--model", choices=["simplecnn", "resnet18"], default="simplecnn",
-                   help="resnet18 = BASELINE config 5 on synthetic ImageNet-shaped data (module path)")
+    p.add_argument("--model", choices=["simplecnn", "resnet18", "resnet50"], default="simplecnn",
+                   help="resnet18 = BASELINE config 5 on synthetic ImageNet-shaped data (module path); resnet50 = "
+                        "the bottleneck network on the same path, wherever a flag says resnet18")
     p.add_argument("--image_size", type=int, default=224, help="resnet18: synthetic image side")
     p.add_argument("--num_classes", type=int, default=1000, help="resnet18: classes")
     p.add_argument("--dataset_size", type=int, default=2048, help="resnet18: synthetic images")
