@@ -18,7 +18,8 @@
 // Epilogue (unsplit): bf16 NHWC store (+ optional bias / ReLU) and, when requested,
 // per-block partial per-channel sum and sum-of-squares of the stored values (the
 // training BatchNorm that follows needs exactly these; fixed-order reduction in
-// bn_finalize).
+// bn_finalize).  The stores, the statistics and the inference form are conv_epilogue.h's,
+// shared with conv_halo.hip and conv_pw.hip.
 //
 // The data gradient reads the OHWI weight itself: its A operand (rows ci, K = co) is the
 // transpose of the stored layout, so the [32 co][BC ci] weight tile is staged as stored
@@ -29,6 +30,7 @@
 #include <type_traits>
 
 #include "kernels/common.h"
+#include "kernels/conv_epilogue.h"
 #include "kernels/conv_infer.h"
 #include "kernels/launchers.h"
 
@@ -46,13 +48,6 @@ constexpr int CG_PIPE = DDP_AMD_CG_PIPE;  // K-steps of global-load lookahead (f
 // LDS-bound, and 40 keeps the LDS footprint smaller.
 constexpr int CG_RS = 40;
 
-// K-slot permutation of the transposed (ds_read_b64_tr_b16) fragment read: fragment
-// element j of lane group g holds k = 4g + j (j < 4) or 16 + 4g + (j - 4).  The matching
-// non-transposed operand is stored to LDS in that order, so it stays one b128 read.
-__device__ __forceinline__ int trk_pos(int k4) {  // LDS position of the 4-group starting at k = 4*k4
-  return k4 < 4 ? 8 * k4 : 8 * (k4 - 4) + 4;
-}
-
 // Stem geometry as constants (SG = 1: ResNet-18's 7x7 / s2 / p3 stem on 224 x 224 inputs,
 // 112 x 112 outputs; SG = 0: runtime).  The stem kernels' per-K-step tap / pixel index math
 // was ~30 VALU instructions per MFMA with runtime divisors (profiles/r4_resnet/pmc).
@@ -69,35 +64,6 @@ inline bool stem_geo_224(const ConvGeom& g) {
          g.OH == 112 && g.OW == 112;
 }
 #define SG_(f, rt) (StemGeo<SG>::f ? StemGeo<SG>::f : (rt))
-
-// Inference epilogue of the 2 x 2-wave MFMA tiling: accumulator (i, j) holds output channels
-// co + 16 i .. + 3 of pixel px + 16 j.  relu?(acc * sc + sh (+ res)) rounded to bf16 once;
-// the residual is one 8-byte load beside the 8-byte store.
-template <int TCO, int TPX, bool RELU>
-__device__ __forceinline__ void infer_epilogue(const f32x4 (&acc)[TCO][TPX], const float4* isc, const float4* ish,
-                                               const bf16_t* __restrict__ res, bf16_t* __restrict__ Y, int Cout,
-                                               int Ptot, int px, int co) {
-#pragma unroll
-  for (int j = 0; j < TPX; ++j) {
-    const int Pj = px + 16 * j;
-    if (Pj >= Ptot) continue;
-#pragma unroll
-    for (int i = 0; i < TCO; ++i) {
-      const long off = (long)Pj * Cout + co + 16 * i;
-      const float sc[4] = {isc[i].x, isc[i].y, isc[i].z, isc[i].w};
-      const float sh[4] = {ish[i].x, ish[i].y, ish[i].z, ish[i].w};
-      float v[4], rv[4] = {0.f, 0.f, 0.f, 0.f};
-      if (res) unpack4(*reinterpret_cast<const uint2*>(res + off), rv);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        v[r] = fmaf(acc[i][j][r], sc[r], sh[r]);
-        if (res) v[r] += rv[r];
-        if (RELU) v[r] = fmaxf(v[r], 0.f);
-      }
-      *reinterpret_cast<uint2*>(Y + off) = pack4(v[0], v[1], v[2], v[3]);
-    }
-  }
-}
 
 // STEM: Cin == 4 (3 real channels + 1 zero pad); a K-step covers 8 taps x 4 channels,
 // k = tap*4 + c, so the weight row [KH*KW*4] is still contiguous per K-step.
@@ -216,15 +182,9 @@ __global__ __launch_bounds__(256) void conv_gemm_fwd_kernel(ConvGeom g, const bf
   if (kb < ke) store_k(0, ra[0], rb[0]);
   // INF: the lane's 4 consecutive output channels of each tile row, requested here so that
   // they land during the K loop
+  const int cl = wco * (BC / 2) + 4 * (lane >> 4);  // the lane's block-local channel of tile row 0
   float4 isc[INF ? TCO : 1], ish[INF ? TCO : 1];
-  if constexpr (INF) {
-#pragma unroll
-    for (int i = 0; i < TCO; ++i) {
-      const int co = co0 + wco * (BC / 2) + 16 * i + 4 * (lane >> 4);
-      isc[i] = *reinterpret_cast<const float4*>(ie.sc + co);
-      ish[i] = *reinterpret_cast<const float4*>(ie.sh + co);
-    }
-  }
+  if constexpr (INF) infer_coef(ie, co0 + cl, isc, ish);
   __syncthreads();
   const int kofs = 8 * (lane >> 4), col = lane & 15;
   for (int base = kb; base < ke; base += CG_PIPE) {
@@ -250,79 +210,19 @@ __global__ __launch_bounds__(256) void conv_gemm_fwd_kernel(ConvGeom g, const bf
     }
   }
 
-  // ---- epilogue
-  if (PART) {  // fp32 split partial [z][P][Cout]: 4 consecutive channels per lane = 16 B
-    float* dst = part + (long)bk.z * Ptot * g.Cout;
-#pragma unroll
-    for (int j = 0; j < TPX; ++j) {
-      const int Pj = p0 + wpx * (BP / 2) + 16 * j + col;
-      if (Pj >= Ptot) continue;
-#pragma unroll
-      for (int i = 0; i < TCO; ++i) {
-        const int co = co0 + wco * (BC / 2) + 16 * i + 4 * (lane >> 4);
-        *reinterpret_cast<float4*>(dst + (long)Pj * g.Cout + co) =
-            make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
-      }
-    }
-    return;
-  }
-  if constexpr (INF) {
-    infer_epilogue<TCO, TPX, RELU>(acc, isc, ish, ie.res, Y, g.Cout, Ptot, p0 + wpx * (BP / 2) + col,
-                                   co0 + wco * (BC / 2) + 4 * (lane >> 4));
-    return;
-  }
-  float csum[TCO][4], csq[TCO][4];
-#pragma unroll
-  for (int i = 0; i < TCO; ++i)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) csum[i][r] = csq[i][r] = 0.f;
-#pragma unroll
-  for (int j = 0; j < TPX; ++j) {
-    const int Pj = p0 + wpx * (BP / 2) + 16 * j + col;
-    const bool ok = Pj < Ptot;
-#pragma unroll
-    for (int i = 0; i < TCO; ++i) {
-      const int co = co0 + wco * (BC / 2) + 16 * i + 4 * (lane >> 4);
-      float v[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        v[r] = acc[i][j][r] + (bias ? bias[co + r] : 0.f);
-        if (RELU) v[r] = fmaxf(v[r], 0.f);
-      }
-      const uint2 pk = pack4(v[0], v[1], v[2], v[3]);
-      if (ok) *reinterpret_cast<uint2*>(Y + (long)Pj * g.Cout + co) = pk;
-      if (STATS) {
-        float q[4];
-        unpack4(pk, q);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float x = ok ? q[r] : 0.f;
-          csum[i][r] += x;
-          csq[i][r] = fmaf(x, x, csq[i][r]);
-        }
-      }
-    }
-  }
-  if (STATS) {
-    // per-block partials: reduce the 16 pixel lanes, then the two pixel-waves via LDS
-    __shared__ float s_st[2][2][BC];
-#pragma unroll
-    for (int i = 0; i < TCO; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float a = sum16(csum[i][r]), b = sum16(csq[i][r]);
-        if (col == 0) {
-          const int cl = wco * (BC / 2) + 16 * i + 4 * (lane >> 4) + r;
-          s_st[wpx][0][cl] = a;
-          s_st[wpx][1][cl] = b;
-        }
-      }
-    __syncthreads();
-    // stats slab: [blocks_x][2][Cout]
-    for (int c = tid; c < BC; c += 256) {
-      float* dst = stats + (long)bk.x * 2 * g.Cout;
-      st_wt(dst + co0 + c, s_st[0][0][c] + s_st[1][0][c]);
-      st_wt(dst + g.Cout + co0 + c, s_st[0][1][c] + s_st[1][1][c]);
+  // ---- epilogue (conv_epilogue.h); the block's pixel columns are consecutive NHWC pixels
+  const int px = p0 + wpx * (BP / 2) + col;
+  auto pix = [&](int j) { return TilePx{px + 16 * j < Ptot, px + 16 * j}; };
+  if constexpr (PART) {  // fp32 split partial [z][P][Cout]
+    part_store(acc, pix, part + (long)bk.z * Ptot * g.Cout, g.Cout, co0 + cl);
+  } else if constexpr (INF) {
+    infer_store(acc, pix, isc, ish, ie.res, RELU, Y, g.Cout, co0 + cl);
+  } else {
+    float csum[TCO][4], csq[TCO][4];
+    train_store<true, RELU, STATS>(acc, pix, bias, Y, g.Cout, co0 + cl, csum, csq);
+    if constexpr (STATS) {
+      __shared__ float s_st[2][2][BC];
+      stats_finish(csum, csq, s_st, cl, wpx, stats + (long)bk.x * 2 * g.Cout + co0, g.Cout);  // slab [blocks_x][2][Cout]
     }
   }
 }
@@ -376,15 +276,9 @@ __global__ __launch_bounds__(256, 2) void conv_stem_halo_fwd_kernel(ConvGeom g, 
       a[kh][i] = __builtin_bit_cast(bf16x8, make_uint4(t0.x, t0.y, t1.x, t1.y));
     }
   }
-  float4 isc[INF ? TCO : 1], ish[INF ? TCO : 1];  // the block's channels: once, like the weights
-  if constexpr (INF) {
-#pragma unroll
-    for (int i = 0; i < TCO; ++i) {
-      const int co = co0 + wco * (BC / 2) + 16 * i + 4 * (lane >> 4);
-      isc[i] = *reinterpret_cast<const float4*>(ie.sc + co);
-      ish[i] = *reinterpret_cast<const float4*>(ie.sh + co);
-    }
-  }
+  const int cl = wco * (BC / 2) + 4 * (lane >> 4);  // the lane's block-local channel of tile row 0
+  float4 isc[INF ? TCO : 1], ish[INF ? TCO : 1];     // the block's channels: once, like the weights
+  if constexpr (INF) infer_coef(ie, co0 + cl, isc, ish);
   // the zero columns of both buffers: j = 0..2 (iw = -3..-1) and j = 227..231 (iw >= 224)
   for (int e = tid; e < 2 * STEM_ROWS * 8; e += 256) {
     const int bf = e / (STEM_ROWS * 8), r = (e >> 3) % STEM_ROWS, k = e & 7;
@@ -454,60 +348,15 @@ __global__ __launch_bounds__(256, 2) void conv_stem_halo_fwd_kernel(ConvGeom g, 
         for (int j = 0; j < TPX; ++j) acc[i][j] = mfma16(a[kh][i], b[j], acc[i][j]);
     }
 
-    // ---- epilogue (conv_gemm_fwd_kernel's, unsplit; stats row = tile)
-    float csum[TCO][4], csq[TCO][4];
-#pragma unroll
-    for (int i = 0; i < TCO; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) csum[i][r] = csq[i][r] = 0.f;
-    if constexpr (INF)
-      infer_epilogue<TCO, TPX, RELU>(acc, isc, ish, ie.res, Y, g.Cout, Ptot, p0 + wpx * (BP / 2) + col,
-                                     co0 + wco * (BC / 2) + 4 * (lane >> 4));
-#pragma unroll
-    for (int j = 0; j < (INF ? 0 : TPX); ++j) {
-      const int Pj = p0 + wpx * (BP / 2) + 16 * j + col;
-      const bool ok = Pj < Ptot;
-#pragma unroll
-      for (int i = 0; i < TCO; ++i) {
-        const int co = co0 + wco * (BC / 2) + 16 * i + 4 * (lane >> 4);
-        float v[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          v[r] = acc[i][j][r] + (bias ? bias[co + r] : 0.f);
-          if (RELU) v[r] = fmaxf(v[r], 0.f);
-        }
-        const uint2 pk = pack4(v[0], v[1], v[2], v[3]);
-        if (ok) *reinterpret_cast<uint2*>(Y + (long)Pj * g.Cout + co) = pk;
-        if (STATS) {
-          float qv[4];
-          unpack4(pk, qv);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float x = ok ? qv[r] : 0.f;
-            csum[i][r] += x;
-            csq[i][r] = fmaf(x, x, csq[i][r]);
-          }
-        }
-      }
-    }
-    if (STATS) {
-#pragma unroll
-      for (int i = 0; i < TCO; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float sa = sum16(csum[i][r]), sb = sum16(csq[i][r]);
-          if (col == 0) {
-            const int cl = wco * (BC / 2) + 16 * i + 4 * (lane >> 4) + r;
-            s_st[wpx][0][cl] = sa;
-            s_st[wpx][1][cl] = sb;
-          }
-        }
-      __syncthreads();
-      for (int c = tid; c < BC; c += 256) {
-        float* dst = stats + (long)t * 2 * g.Cout;
-        st_wt(dst + co0 + c, s_st[0][0][c] + s_st[1][0][c]);
-        st_wt(dst + g.Cout + co0 + c, s_st[0][1][c] + s_st[1][1][c]);
-      }
+    // ---- epilogue (conv_epilogue.h; unsplit, stats row = tile)
+    const int px = p0 + wpx * (BP / 2) + col;
+    auto pix = [&](int j) { return TilePx{px + 16 * j < Ptot, px + 16 * j}; };
+    if constexpr (INF) {
+      infer_store(acc, pix, isc, ish, ie.res, RELU, Y, g.Cout, co0 + cl);
+    } else {
+      float csum[TCO][4], csq[TCO][4];
+      train_store<true, RELU, STATS>(acc, pix, bias, Y, g.Cout, co0 + cl, csum, csq);
+      if constexpr (STATS) stats_finish(csum, csq, s_st, cl, wpx, stats + (long)t * 2 * g.Cout + co0, g.Cout);
     }
     if (t + 1 < t_end) store_x(cur ^ 1, xr[cur ^ 1]);  // tile t + 1 (buffer cur ^ 1 was last read a tile ago)
     __syncthreads();
@@ -656,35 +505,19 @@ __global__ __launch_bounds__(256) void conv_gemm_dgrad_kernel(ConvGeom g, const 
     }
   }
   const long Ptot = (long)g.N * g.H * g.W;
-#pragma unroll
-  for (int j = 0; j < TPX; ++j) {
+  auto pix = [&](int j) {  // class pixel -> NHWC pixel index
     const int Pj = p0 + wpx * (BP / 2) + 16 * j + col;
-    if (Pj >= Pc) continue;
-    long gp = Pj;  // class pixel -> NHWC pixel index
+    long gp = Pj;
     if (parity) {
       const int n = Pj / HWc;
       const int r = Pj - n * HWc;
       const int i = r / Wc;
       gp = ((long)n * g.H + ts * i + ph) * g.W + ts * (r - i * Wc) + pw;
     }
-#pragma unroll
-    for (int i = 0; i < TCI; ++i) {
-      const int ci = ci0b + wci * (BC / 2) + 16 * i + 4 * (lane >> 4);
-      float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-      if (PART) {
-        *reinterpret_cast<float4*>(part + ((long)zs * Ptot + gp) * g.Cin + ci) =
-            make_float4(v[0], v[1], v[2], v[3]);
-        continue;
-      }
-      if (MASK_X) {
-        float xm[4];
-        unpack4(*reinterpret_cast<const uint2*>(Xact + gp * g.Cin + ci), xm);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = xm[r] > 0.f ? v[r] : 0.f;
-      }
-      *reinterpret_cast<uint2*>(dX + gp * g.Cin + ci) = pack4(v[0], v[1], v[2], v[3]);
-    }
-  }
+    return TilePx{Pj < Pc, gp};
+  };
+  dgrad_store<MASK_X, PART>(acc, pix, Xact, dX, part + (long)zs * Ptot * g.Cin, g.Cin,
+                            ci0b + wci * (BC / 2) + 4 * (lane >> 4));
 }
 
 // ---------------------------------------------------------------- split-K reduction

@@ -11,13 +11,14 @@
 // barrier step and stored to the other halo buffer before the chunk switch.
 //
 // Same MFMA tiling as conv_gemm_fwd_kernel (4 waves = 2 co x 2 px, 16x16x32 bf16,
-// 128-pixel column tile of which R*W are live), same epilogues: bf16 NHWC store with the
+// 128-pixel column tile of which R*W are live), same epilogues (conv_epilogue.h): bf16 NHWC store with the
 // per-block BatchNorm sum / sum-of-squares partials, or fp32 split-K partials for
 // splitk_reduce.  K splits run over channel chunks (grid.z).
 #include <stdexcept>
 
 #include "kernels/bn_affine.h"
 #include "kernels/common.h"
+#include "kernels/conv_epilogue.h"
 #include "kernels/conv_infer.h"
 #include "kernels/launchers.h"
 
@@ -146,15 +147,9 @@ __global__ __launch_bounds__(256) void conv3x3s1_halo_fwd_kernel(ConvGeom g, con
     store_w(0, ra);
   }
   // INF: the lane's 4 consecutive output channels per tile row, in flight during the K loop
+  const int cl = wco * (BC / 2) + 4 * (lane >> 4);  // the lane's block-local channel of tile row 0
   float4 isc[INF ? TCO : 1], ish[INF ? TCO : 1];
-  if constexpr (INF) {
-#pragma unroll
-    for (int i = 0; i < TCO; ++i) {
-      const int co = co0 + wco * (BC / 2) + 16 * i + 4 * (lane >> 4);
-      isc[i] = *reinterpret_cast<const float4*>(ie.sc + co);
-      ish[i] = *reinterpret_cast<const float4*>(ie.sh + co);
-    }
-  }
+  if constexpr (INF) infer_coef(ie, co0 + cl, isc, ish);
   __syncthreads();
   int step = 0;
   for (int ch = c_beg; ch < c_end; ++ch) {
@@ -187,79 +182,25 @@ __global__ __launch_bounds__(256) void conv3x3s1_halo_fwd_kernel(ConvGeom g, con
     }
   }
 
-  // ---- epilogue (block-local pixel p -> output row oh0 + p / W, column p % W)
-  const int Ptot = g.N * g.OH * g.OW;
-  float csum[TCO][4], csq[TCO][4];
-#pragma unroll
-  for (int i = 0; i < TCO; ++i)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) csum[i][r] = csq[i][r] = 0.f;
-#pragma unroll
-  for (int j = 0; j < TPX; ++j) {
+  // ---- epilogue (conv_epilogue.h): block-local pixel p -> output row oh0 + p / W, column p % W
+  auto pix = [&](int j) {
     const int p = wpx * (BP / 2) + 16 * j + col;
     const int r = p / W;
     const int oh = oh0 + r;
-    const bool ok = p < NPX && oh < g.OH;
-    const long P = ((long)n_ * g.OH + oh) * g.OW + (p - r * W);
-#pragma unroll
-    for (int i = 0; i < TCO; ++i) {
-      const int co = co0 + wco * (BC / 2) + 16 * i + 4 * (lane >> 4);
-      if (PART) {
-        if (ok)
-          *reinterpret_cast<float4*>(part + ((long)bk.z * Ptot + P) * g.Cout + co) =
-              make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
-        continue;
-      }
-      if constexpr (INF) {
-        if (ok) {
-          const float sc[4] = {isc[i].x, isc[i].y, isc[i].z, isc[i].w};
-          const float sh[4] = {ish[i].x, ish[i].y, ish[i].z, ish[i].w};
-          float v[4], rv[4] = {0.f, 0.f, 0.f, 0.f};
-          if (ie.res) unpack4(*reinterpret_cast<const uint2*>(ie.res + P * g.Cout + co), rv);
-#pragma unroll
-          for (int rr = 0; rr < 4; ++rr) {
-            v[rr] = fmaf(acc[i][j][rr], sc[rr], sh[rr]);
-            if (ie.res) v[rr] += rv[rr];
-            if (ie.relu) v[rr] = fmaxf(v[rr], 0.f);
-          }
-          *reinterpret_cast<uint2*>(Y + P * g.Cout + co) = pack4(v[0], v[1], v[2], v[3]);
-        }
-        continue;
-      }
-      const uint2 pk = pack4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
-      if (ok) *reinterpret_cast<uint2*>(Y + P * g.Cout + co) = pk;
-      if (STATS) {
-        float q[4];
-        unpack4(pk, q);
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-          const float x = ok ? q[rr] : 0.f;
-          csum[i][rr] += x;
-          csq[i][rr] = fmaf(x, x, csq[i][rr]);
-        }
-      }
-    }
-  }
-  if (STATS && !PART) {
-    // the weight tiles are dead after the K loop: their LDS holds the per-wave partials
-    // (keeps two blocks per CU resident)
-    float (*s_st)[2][BC] = reinterpret_cast<float (*)[2][BC]>(&sA[0][0]);
-#pragma unroll
-    for (int i = 0; i < TCO; ++i)
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const float a = sum16(csum[i][rr]), b = sum16(csq[i][rr]);
-        if (col == 0) {
-          const int cl = wco * (BC / 2) + 16 * i + 4 * (lane >> 4) + rr;
-          s_st[wpx][0][cl] = a;
-          s_st[wpx][1][cl] = b;
-        }
-      }
-    __syncthreads();
-    for (int c = tid; c < BC; c += 256) {
-      float* dst = stats + (long)bk.x * 2 * g.Cout;
-      st_wt(dst + co0 + c, s_st[0][0][c] + s_st[1][0][c]);
-      st_wt(dst + g.Cout + co0 + c, s_st[0][1][c] + s_st[1][1][c]);
+    return TilePx{p < NPX && oh < g.OH, ((long)n_ * g.OH + oh) * g.OW + (p - r * W)};
+  };
+  if constexpr (PART) {
+    part_store(acc, pix, part + (long)bk.z * g.N * g.OH * g.OW * g.Cout, g.Cout, co0 + cl);
+  } else if constexpr (INF) {
+    infer_store(acc, pix, isc, ish, ie.res, ie.relu != 0, Y, g.Cout, co0 + cl);
+  } else {
+    float csum[TCO][4], csq[TCO][4];
+    train_store<false, false, STATS>(acc, pix, nullptr, Y, g.Cout, co0 + cl, csum, csq);
+    if constexpr (STATS) {
+      // the weight tiles are dead after the K loop: their LDS holds the per-wave partials
+      // (keeps two blocks per CU resident)
+      stats_finish(csum, csq, reinterpret_cast<float (*)[2][BC]>(&sA[0][0]), cl, wpx,
+                   stats + (long)bk.x * 2 * g.Cout + co0, g.Cout);
     }
   }
 }
@@ -270,8 +211,7 @@ __global__ __launch_bounds__(256) void conv3x3s1_halo_fwd_kernel(ConvGeom g, con
 // dY[ih + 1 - kh][iw + 1 - kw][co].  Same halo tiling over dY rows; the weight tiles of
 // one kernel row are staged as stored ([32 co][BC ci] per tap) and read with
 // ds_read_b64_tr_b16, so the dY halo is stored in the transposed read's K order
-// (dtrk_pos, as conv_gemm_dgrad_kernel does for its gathered tile).
-__device__ __forceinline__ int dtrk_pos(int k4) { return k4 < 4 ? 8 * k4 : 8 * (k4 - 4) + 4; }
+// (trk_pos, as conv_gemm_dgrad_kernel does for its gathered tile).
 
 template <int BC, int BP, bool MASK_X, bool PART, int GW = 0>  // GW: see the forward kernel
 __global__ __launch_bounds__(256) void conv3x3s1_halo_dgrad_kernel(ConvGeom g, const bf16_t* __restrict__ dY,
@@ -322,8 +262,8 @@ __global__ __launch_bounds__(256) void conv3x3s1_halo_dgrad_kernel(ConvGeom g, c
       const int hp = e >> 2, qq = e & 3;
       if (hp < HPX) {
         const uint4 q = __builtin_bit_cast(uint4, rh[u]);
-        *reinterpret_cast<uint2*>(&sH[buf][hp * HL_RS + dtrk_pos(2 * qq)]) = make_uint2(q.x, q.y);
-        *reinterpret_cast<uint2*>(&sH[buf][hp * HL_RS + dtrk_pos(2 * qq + 1)]) = make_uint2(q.z, q.w);
+        *reinterpret_cast<uint2*>(&sH[buf][hp * HL_RS + trk_pos(2 * qq)]) = make_uint2(q.x, q.y);
+        *reinterpret_cast<uint2*>(&sH[buf][hp * HL_RS + trk_pos(2 * qq + 1)]) = make_uint2(q.z, q.w);
       }
     }
   };
@@ -405,32 +345,14 @@ __global__ __launch_bounds__(256) void conv3x3s1_halo_dgrad_kernel(ConvGeom g, c
     }
   }
 
-  const long Ptot = (long)g.N * H * W;
-#pragma unroll
-  for (int j = 0; j < TPX; ++j) {
+  auto pix = [&](int j) {  // block-local pixel p -> input row ih0 + p / W, column p % W
     const int p = wpx * (BP / 2) + 16 * j + col;
     const int r = p / W;
     const int ih = ih0 + r;
-    if (p >= NPX || ih >= H) continue;
-    const long P = ((long)n_ * H + ih) * W + (p - r * W);
-#pragma unroll
-    for (int i = 0; i < TCI; ++i) {
-      const int ci = ci0 + wci * (BC / 2) + 16 * i + 4 * (lane >> 4);
-      float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-      if (PART) {
-        *reinterpret_cast<float4*>(part + ((long)bk.z * Ptot + P) * g.Cin + ci) =
-            make_float4(v[0], v[1], v[2], v[3]);
-        continue;
-      }
-      if (MASK_X) {
-        float xm[4];
-        unpack4(*reinterpret_cast<const uint2*>(Xact + P * g.Cin + ci), xm);
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) v[rr] = xm[rr] > 0.f ? v[rr] : 0.f;
-      }
-      *reinterpret_cast<uint2*>(dX + P * g.Cin + ci) = pack4(v[0], v[1], v[2], v[3]);
-    }
-  }
+    return TilePx{p < NPX && ih < H, ((long)n_ * H + ih) * W + (p - r * W)};
+  };
+  dgrad_store<MASK_X, PART>(acc, pix, Xact, dX, part + (long)bk.z * g.N * H * W * g.Cin, g.Cin,
+                            ci0 + wci * (BC / 2) + 4 * (lane >> 4));
 }
 
 void conv_halo_dgrad(const ConvGeom& g, int bp, int bc, int splits, const bf16_t* dY, const bf16_t* Wt,

@@ -30,7 +30,7 @@
 //   [64][BM] and X [64][BN] exactly as stored (pixel rows, 16-byte pieces; row stride BM+16 /
 //   BN+16 = an odd multiple of 8 dwords) and both MFMA fragments are read with
 //   ds_read_b64_tr_b16.  Both operands take the transposed read, so both see the same K-slot
-//   order (conv_gemm.hip trk_pos: k = 4g + j, 16 + 4g + j) and no operand is permuted when
+//   order (conv_epilogue.h trk_pos: k = 4g + j, 16 + 4g + j) and no operand is permuted when
 //   stored.  AFF applies the deferred affine to X while staging (a thread keeps one channel
 //   group for the whole K loop: its sc / sh stay in 16 registers).  Pixels are split into
 //   chunks of `ppc` on grid.z: one chunk writes dW (fp32, `accum` adds to it), several write
@@ -44,6 +44,7 @@
 
 #include "kernels/bn_affine.h"
 #include "kernels/common.h"
+#include "kernels/conv_epilogue.h"
 #include "kernels/conv_infer.h"
 #include "kernels/launchers.h"
 
@@ -126,15 +127,9 @@ __global__ __launch_bounds__(256) void conv_pw_fwd_kernel(const bf16_t* __restri
   }
   // PW_INFER: the lane's 4 consecutive output channels of each tile row, requested here so
   // that they land during the K loop
+  const int cl = wco * (BC / 2) + 4 * (lane >> 4);  // the lane's block-local channel of tile row 0
   float4 isc[EPI == PW_INFER ? TCO : 1], ish[EPI == PW_INFER ? TCO : 1];
-  if constexpr (EPI == PW_INFER) {
-#pragma unroll
-    for (int i = 0; i < TCO; ++i) {
-      const int co = co0 + wco * (BC / 2) + 16 * i + 4 * (lane >> 4);
-      isc[i] = *reinterpret_cast<const float4*>(ie.sc + co);
-      ish[i] = *reinterpret_cast<const float4*>(ie.sh + co);
-    }
-  }
+  if constexpr (EPI == PW_INFER) infer_coef(ie, co0 + cl, isc, ish);
   store_k(0, 0, ra, rb);
   __syncthreads();
   const int kofs = 8 * (lane >> 4), col = lane & 15;
@@ -160,75 +155,17 @@ __global__ __launch_bounds__(256) void conv_pw_fwd_kernel(const bf16_t* __restri
     __syncthreads();
   }
 
-  // ---- epilogue: accumulator (i, j) = channels co + 16 i .. + 3 of pixel px + 16 j
-  const int px = p0 + wpx * (BP / 2) + col, cob = co0 + wco * (BC / 2) + 4 * (lane >> 4);
+  // ---- epilogue (conv_epilogue.h); the block's pixel columns are consecutive rows of Y
+  const int px = p0 + wpx * (BP / 2) + col;
+  auto pix = [&](int j) { return TilePx{px + 16 * j < P, px + 16 * j}; };
   if constexpr (EPI == PW_INFER) {
-#pragma unroll
-    for (int j = 0; j < TPX; ++j) {
-      const int Pj = px + 16 * j;
-      if (Pj >= P) continue;
-#pragma unroll
-      for (int i = 0; i < TCO; ++i) {
-        const long off = (long)Pj * Cout + cob + 16 * i;
-        const float sc[4] = {isc[i].x, isc[i].y, isc[i].z, isc[i].w};
-        const float sh[4] = {ish[i].x, ish[i].y, ish[i].z, ish[i].w};
-        float v[4], rv[4] = {0.f, 0.f, 0.f, 0.f};
-        if (ie.res) unpack4(*reinterpret_cast<const uint2*>(ie.res + off), rv);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          v[r] = fmaf(acc[i][j][r], sc[r], sh[r]);
-          if (ie.res) v[r] += rv[r];
-          if (ie.relu) v[r] = fmaxf(v[r], 0.f);
-        }
-        *reinterpret_cast<uint2*>(Y + off) = pack4(v[0], v[1], v[2], v[3]);
-      }
-    }
-    return;
-  }
-  float csum[TCO][4], csq[TCO][4];
-#pragma unroll
-  for (int i = 0; i < TCO; ++i)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) csum[i][r] = csq[i][r] = 0.f;
-#pragma unroll
-  for (int j = 0; j < TPX; ++j) {
-    const int Pj = px + 16 * j;
-    const bool ok = Pj < P;
-#pragma unroll
-    for (int i = 0; i < TCO; ++i) {
-      const uint2 pk = pack4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
-      if (ok) *reinterpret_cast<uint2*>(Y + (long)Pj * Cout + cob + 16 * i) = pk;
-      if constexpr (EPI == PW_STATS) {
-        float q[4];
-        unpack4(pk, q);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float x = ok ? q[r] : 0.f;
-          csum[i][r] += x;
-          csq[i][r] = fmaf(x, x, csq[i][r]);
-        }
-      }
-    }
-  }
-  if constexpr (EPI == PW_STATS) {
-    // per-block partials: the 16 pixel lanes, then the two pixel waves through LDS
-    __shared__ float s_st[2][2][BC];
-#pragma unroll
-    for (int i = 0; i < TCO; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float a = sum16(csum[i][r]), b = sum16(csq[i][r]);
-        if (col == 0) {
-          const int cl = wco * (BC / 2) + 16 * i + 4 * (lane >> 4) + r;
-          s_st[wpx][0][cl] = a;
-          s_st[wpx][1][cl] = b;
-        }
-      }
-    __syncthreads();
-    if (tid < BC) {
-      float* dst = stats + (long)bk.x * 2 * Cout + co0 + tid;
-      st_wt(dst, s_st[0][0][tid] + s_st[1][0][tid]);
-      st_wt(dst + Cout, s_st[0][1][tid] + s_st[1][1][tid]);
+    infer_store(acc, pix, isc, ish, ie.res, ie.relu != 0, Y, Cout, co0 + cl);
+  } else {
+    float csum[TCO][4], csq[TCO][4];
+    train_store<false, false, EPI == PW_STATS>(acc, pix, nullptr, Y, Cout, co0 + cl, csum, csq);
+    if constexpr (EPI == PW_STATS) {
+      __shared__ float s_st[2][2][BC];
+      stats_finish(csum, csq, s_st, cl, wpx, stats + (long)bk.x * 2 * Cout + co0, Cout);
     }
   }
 }

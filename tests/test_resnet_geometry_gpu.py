@@ -99,7 +99,11 @@ def conv_case(*geo):
     return _CACHE[geo]
 
 
-def run_fwd(C, cv, bp, bc, splits, halo, want_halo=None):
+def run_fwd(C, cv, bp, bc, splits, halo, want_halo=None, bias=None, relu=False, with_stats=True):
+    """`bias` / `relu`: the gathered kernel's bias + ReLU epilogue (unsplit, never the halo tile).
+    The bias is one more term of the accumulated sum (n + 1 terms, A + |bias|); ReLU is
+    1-Lipschitz, so the accumulation bound carries over and the one rounding is of the clamped
+    value - the same formula against relu(ref)."""
     N, H, W, Cin, Cout, K, s, p = cv.geo
     y = Guarded((N, cv.OH, cv.OW, Cout), BF)
     pbp, pbc, sp, rows, _, hl = C.conv_gemm_plan(cv.x, y.t, K, K, s, p, False, bp, bc, splits, -1, halo)
@@ -107,14 +111,17 @@ def run_fwd(C, cv, bp, bc, splits, halo, want_halo=None):
         assert hl == want_halo, (cv.geo, hl)
     if splits > 0:
         assert sp == splits
-    stats = Guarded((rows, 2, Cout), torch.float32)
+    stats = Guarded((rows, 2, Cout), torch.float32) if with_stats else None
     part = Guarded((sp * y.t.numel(),), torch.float32) if sp > 1 else None
-    C.conv_gemm_fwd(cv.x, cv.w, None, y.t, K, K, s, p, False, stats.t, part.t if part else None, bp, bc,
-                    splits, halo)
+    C.conv_gemm_fwd(cv.x, cv.w, bias, y.t, K, K, s, p, relu, stats.t if stats else None, part.t if part else None,
+                    bp, bc, splits, halo)
     torch.cuda.synchronize()
-    what = f"fwd {cv.geo} plan bp={pbp} bc={pbc} splits={sp} halo={hl}"
-    r = ratio_bf16(y.t, cv.y_ref, cv.y_abs, K * K * Cin, what)
-    rs = ratio_stats(stats.t, y.t, what)
+    what = f"fwd {cv.geo} plan bp={pbp} bc={pbc} splits={sp} halo={hl} bias={bias is not None} relu={relu}"
+    ref, A, n = cv.y_ref, cv.y_abs, K * K * Cin
+    if bias is not None:
+        ref, A, n = ref + f64(bias), A + f64(bias).abs(), n + 1
+    r = ratio_bf16(y.t, torch.relu(ref) if relu else ref, A, n, what)
+    rs = ratio_stats(stats.t, y.t, what) if stats else 0.0
     for g_ in (y, stats, part):
         if g_ is not None:
             g_.check(what)
@@ -211,6 +218,13 @@ def test_stride1_fwd_stats(C, N, H, W, Cin, Cout):
     if Cout % 128 == 0:  # the 128-channel halo tile
         r, rs, _ = run_fwd(C, cv, 0, 128, 1, 1, 1)
         report("fwd_halo", cv.geo, r)
+    # the gathered kernel's other epilogue builds: no statistics, and bias + ReLU with and without them
+    b = rnd(Cout, scale=0.5, seed=11, dtype=torch.float32)
+    for kw in (dict(with_stats=False), dict(bias=b, relu=True), dict(bias=b, relu=True, with_stats=False)):
+        r, rs, _ = run_fwd(C, cv, 0, 0, 1, 0, 0, **kw)
+        report("fwd_gemm", cv.geo, r)
+        if kw.get("with_stats", True):
+            report("stats", cv.geo, rs)
 
 
 @pytest.mark.parametrize("N,H,W,Cin,Cout", S1)
@@ -345,6 +359,14 @@ def test_stem_odd_and_nonsquare(C, N, H, W):
             stats.check("stem stats")
         ys.append(y.t)
     assert torch.equal(ys[0], ys[1])
+    # the bias + ReLU build (see run_fwd for the bound)
+    b = rnd(64, scale=0.5, seed=11, dtype=torch.float32)
+    y = Guarded((N, OH, OW, 64), BF)
+    C.conv_gemm_fwd(x4, w4, b, y.t, 7, 7, 2, 3, True, None)
+    torch.cuda.synchronize()
+    report("stem_fwd", geo, ratio_bf16(y.t, torch.relu(y_ref + f64(b)), y_abs + f64(b).abs(), 148,
+                                       f"stem fwd {geo} bias + relu"))
+    y.check("stem y bias + relu")
     # weight gradient [Cout][7][7][3] (the pad channel is dropped)
     dw_ref = nhwc(torch.nn.grad.conv2d_weight(xd, wd.shape, dyd, **kw)).reshape(-1)
     dw_abs = nhwc(torch.nn.grad.conv2d_weight(xd.abs(), wd.shape, dyd.abs(), **kw)).reshape(-1)

@@ -204,6 +204,11 @@ def test_stem_conv_7x7_s2(N, H):
     yf = y.float().view(-1, 64)
     assert relerr(stats[:, 0].sum(0), yf.sum(0)) < 1e-4
     assert relerr(stats[:, 1].sum(0), (yf * yf).sum(0)) < 1e-4
+    # the bias + ReLU build of the same kernels
+    b = rnd(64, scale=0.5, seed=11, dtype=torch.float32)
+    y3 = torch.empty_like(y)
+    C.conv_gemm_fwd(x4, w4, b, y3, 7, 7, 2, 3, True, None)
+    assert relerr(y3, torch.relu(ref + b)) < 1e-2
     dy = rnd(N, OH, OH, 64, seed=5)
     rdw = torch.nn.grad.conv2d_weight(x4[..., :3].float().permute(0, 3, 1, 2), (64, 3, 7, 7),
                                       dy.float().permute(0, 3, 1, 2), stride=2, padding=3)
